@@ -2,6 +2,7 @@
 """Headline benchmark: SART+TV (one ASD-POCS outer iteration) at 512^3 x 90 tilts.
 
     python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--n 1024 --nslice 1024 --nproj 120]
+                    [--dump-outputs DIR] [--full [--quick]]
 
 A step = one ASD-POCS outer iteration (examples/sim_ASD.py:66-94): copy_recon, one SART sweep over all tilts, step
 norm, data distance (a full forward projection), copy_recon, 10 TV gradient-descent steps, step norm (the engine forms
@@ -15,10 +16,18 @@ BASELINE's metric: ONE 512^3 x 90 volume on 1/2/4/8 GPUs) shards the --nslice sl
 ``--scaling weak`` gives every rank its own --nslice slices.  The only cross-rank traffic is one scalar all-reduce per
 iteration + one per TV step, and the TV halo planes.  Rank 0 prints ONE JSON line.
 
-At N = 1 the same process then times, as sub-objects of that line (``secondary``): config 2 (256^3 x 60 SART), config 3
-(512^3 x 90 FISTA, roofline of the fused FGP iteration), the 8-GPU shard of config 4 (128 x 1024^2 x 120 ASD-POCS),
-ASD-POCS in the CPU reference's ART form, a normalised-SIRT iteration with the tile projectors' three roofs -- and the
-CPU baselines (``cpu_baseline`` + configs 1 and 2).  ``--quick`` skips the secondary part.
+A plain run does only what the headline needs: set up, warm up, time the --steps steps, write the outputs (--dump-outputs)
+and print the line.  ``--full`` adds everything else, as sub-objects of the same line: the per-kernel roofline records of the
+timed steps (HIP events on the launches), the store-skipping and isolated-kernel figures, the in-process facade's host cost,
+the sharded run's record and parity check against one whole-volume engine (N > 1), and at N = 1 the secondary configs
+(``secondary``): config 2 (256^3 x 60 SART), config 3 (512^3 x 90 FISTA, roofline of the fused FGP iteration), the 8-GPU
+shard of config 4 (128 x 1024^2 x 120 ASD-POCS), ASD-POCS in the CPU reference's ART form, a normalised-SIRT iteration with
+the tile projectors' three roofs -- and the CPU baselines (``cpu_baseline`` + configs 1 and 2).  ``--full --quick`` skips the
+secondary configs and the CPU baselines.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last timed step computed (see ``dump_outputs``): the
+reconstruction and the iteration's two scalars, as .npy files.  The inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 import argparse
 import json
@@ -467,7 +476,7 @@ def _shard_step(nloc, n, nproj, steps=10):
     anything else in a process does; this one has long been running kernels through the C ABI)."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    cmd = [sys.executable, os.path.abspath(__file__), "--force-dist", "--quick", "--nslice", str(nloc), "--nray", str(n),
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--force-dist", "--quick", "--nslice", str(nloc), "--nray", str(n),
            "--nproj", str(nproj), "--steps", str(steps), "--warmup", "2"]
     try:
         p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
@@ -783,6 +792,38 @@ def sharded_run_record(t, comm, rank, world, nglobal, n, nproj, ang, args, round
     return rec
 
 
+DUMP_SEED = 20240917             # the voxel sample of --dump-outputs (fixed: the same voxels in every run of one shape)
+DUMP_SAMPLE = 1 << 22            # 4 Mi voxels = 16 MiB of float32
+DUMP_WHOLE_BYTES = 32 << 20      # a reconstruction up to this size is written whole
+DUMP_SLICE_BYTES = 24 << 20      # budget of the whole slices written beside the sample
+
+
+def dump_outputs(d, vol, dd, tv):
+    """What the last timed step handed its caller, as DIR/<name>.npy (at most ~40 MiB in all):
+      final_dd.npy, final_tv.npy   float64, shape (1,): the step's data distance and TV value (the line's final_dd / final_tv)
+      recon.npy                    float32 (Nslice, Ny, Nz): the reconstruction, when it is at most 32 MiB; larger ones as
+      recon_sample.npy             float32: the voxels at np.unique(default_rng(DUMP_SEED).integers(0, Nslice*Ny*Nz, 4 Mi)) of
+                                   the flattened volume, and
+      recon_slices.npy             float32 (k, Ny, Nz): the k <= 8 whole slices np.linspace(0, Nslice - 1, k) rounded, as many
+                                   as fit in 24 MiB (none when one does not).
+    Returns the names written."""
+    os.makedirs(d, exist_ok=True)
+    files = {"final_dd": np.array([dd], np.float64), "final_tv": np.array([tv], np.float64)}
+    vol = np.asarray(vol, np.float32)
+    if vol.nbytes <= DUMP_WHOLE_BYTES:
+        files["recon"] = vol
+    else:
+        flat = vol.reshape(-1)
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, flat.size, DUMP_SAMPLE))
+        files["recon_sample"] = flat[idx]
+        k = min(8, vol.shape[0], DUMP_SLICE_BYTES // max(1, vol[0].nbytes))
+        if k > 0:
+            files["recon_slices"] = vol[np.unique(np.linspace(0, vol.shape[0] - 1, k).round().astype(np.int64))]
+    for name, a in files.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return sorted(files)
+
+
 # ---- launcher: a plain `python bench.py --gpus N` starts its own N ranks ---------------------------------------------------
 def _free_port():
     with socket.socket() as s:
@@ -864,9 +905,15 @@ def main():
     ap.add_argument("--nproj", type=int, default=90)
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="strong: ONE volume of --nslice slices sharded over the GPUs (BASELINE's metric); weak: --nslice per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel rooflines, store-skipping and isolated-kernel figures, facade cost, "
+                         "sharded parity check, secondary configs and CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (reconstruction or a fixed sample of it, final_dd, final_tv) as DIR/<name>.npy "
+                         "(bench_outputs/ in the tree is ignored by git)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--quick", action="store_true", help="headline only: no secondary configs, no CPU baselines")
-    ap.add_argument("--no-kernel-log", action="store_true", help="experiment: time the steps without the per-launch HIP events (no roofline)")
+    ap.add_argument("--quick", action="store_true", help="with --full: no secondary configs, no CPU baselines")
+    ap.add_argument("--no-kernel-log", action="store_true", help="experiment, with --full: time the steps without the per-launch HIP events (no roofline)")
     ap.add_argument("--force-dist", action="store_true", help="use the slab-sharded engine + its communicator even with one rank")
     ap.add_argument("--no-validate", action="store_true", help="sharded runs: skip the parity check against one whole-volume engine")
     ap.add_argument("--backend", default="nccl", help="process-group backend (nccl = RCCL); tests drive the launcher with gloo")
@@ -875,6 +922,8 @@ def main():
                     help="run the GPU's slab as K sub-slab engines side by side (engine.py: _GroupBackend; single GPU only). "
                          "Measured -1...-3 %% per step at K = 2 and box-dependent, so the default is one engine")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         if args.backend == "nccl":
@@ -984,7 +1033,7 @@ def main():
     else:
         LOG_STRIDE = {K_FUSED_NAME: 1 if two_chains else 4, K_TVN_NAME: 2, K_TVU_NAME: 2}
         log_ids = {K_FUSED_NAME: K_SART_FUSED, K_BP_NAME: K_BP_ANGLE, K_FP_NAME: 1, K_TVN_NAME: 2, K_TVU_NAME: 3}
-    log = KernelLog(t, log_ids, LOG_STRIDE) if on_gpu and not args.no_kernel_log else None
+    log = KernelLog(t, log_ids, LOG_STRIDE) if on_gpu and args.full and not args.no_kernel_log else None
     sync()
     rounds0 = comm_rounds(t)
     t0 = time.perf_counter()
@@ -995,9 +1044,15 @@ def main():
     el = time.perf_counter() - t0
     rounds1 = comm_rounds(t)
     prof = log.read() if log else {}
+    dumped = None
+    if args.dump_outputs:                   # before anything below runs more steps on the engine
+        vol = t.get_volume(dst=0) if comm is not None else t.get_volume()      # sharded: a collective, the whole volume on rank 0
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, vol, dd, tv)
+        del vol
     iso = None
     chains = 1 if resident else sart_chains(t)          # launch chains per sweep of this rank's slab, as the engine runs them now
-    if on_gpu and getattr(t, "sub_slabs", 1) == 1 and chains > 1 and not resident:
+    if args.full and on_gpu and getattr(t, "sub_slabs", 1) == 1 and chains > 1 and not resident:
         # the dominant kernel alone on the chip (one chain, one stream), one untimed step: the kernel's own rate
         t.set_option("sart_streams", 1)
         log1 = KernelLog(t, {K_FUSED_NAME: K_SART_FUSED})
@@ -1012,7 +1067,7 @@ def main():
     # Transparency: k_sart_tile stores only the 256-byte pieces whose bits changed (voxels held at zero by the positivity
     # clamp, rays with a zero residual -- data-dependent).  The same step with every voxel stored, timed after the timed region:
     el_all = None
-    if on_gpu and tile and not resident and not any(o.replace(" ", "").startswith("sart_skip_same=") for o in args.opt):
+    if args.full and on_gpu and tile and not resident and not any(o.replace(" ", "").startswith("sart_skip_same=") for o in args.opt):
         t.set_option("sart_skip_same", 0)
         asd_pocs_step(t, st)
         sync()
@@ -1035,7 +1090,7 @@ def main():
             per_rank = [float(v) for v in allv.tolist()]
 
     comm_record = None
-    if comm is not None and on_gpu:
+    if args.full and comm is not None and on_gpu:
         comm_record = sharded_run_record(t, comm, rank, world, nglobal, n, nproj, ang, args, rounds0, rounds1)
 
     if rank == 0:
@@ -1067,7 +1122,8 @@ def main():
             # what an in-place read-modify-write pass over the slab reaches on this part in any access pattern
             # (tools/micro/copy_patterns.hip: 5.2-5.5 TB/s) -- informative, not the peak
             roofs[name]["frac_of_measured_rmw_ceiling"] = roofs[name]["achieved"] / RMW_CEILING_GBS
-        attach_traffic(roofs, (nloc, n, nproj))
+        if roofs:
+            attach_traffic(roofs, (nloc, n, nproj))
         dominant = max(roofs.values(), key=lambda r: r["total_ms"] * r["sample_stride"]) if roofs else None
         if iso is not None and dominant is not None:
             r1 = roof(K_FUSED_NAME, iso[0], iso[1], alg_bytes[K_FUSED_NAME], busy_ms=iso[2])
@@ -1100,29 +1156,35 @@ def main():
                        "sharding": f"tilt-axis slabs x{world} ({args.scaling} scaling)",
                        "sub_slab_engines_per_gpu": getattr(t, "sub_slabs", 1), "sart_chains_per_engine": chains,
                        "forms": engine_forms(t), "engine": engine_facts(t)},
-            # the data-INDEPENDENT figure (k_sart_tile storing every voxel; the headline skips stores of unchanged 256-byte pieces,
-            # which the zero background of the synthetic phantom favours): null when the option was forced on the command line
-            # (round 5, resident sweep: every voxel is loaded and stored once per sweep whatever the data -- the headline IS that figure)
-            "ms_per_step_every_voxel_stored": (el / args.steps * 1e3 if resident else None) if el_all is None else el_all * 1e3,
             "sart_sweep_form": "k_sart_resident (one launch per sweep, volume resident in registers)" if resident else "k_sart_tile chain (one fused step per angle)",
             "final_dd": dd, "final_tv": tv,
-            "store_skipping": None if el_all is None else {
-                "ms_per_step_with_every_voxel_stored": el_all * 1e3,
-                "note": "k_sart_tile (in place) skips the store of 256-byte pieces whose bits did not change; bit-identical results; the "
-                        "gain depends on the data (zero background of the synthetic phantom); --opt sart_skip_same=0 times the other form"},
-            # N > 1 (and --force-dist): what the run itself can prove about its communication
-            "comm": comm_record,
-            # the plain-process multi-GPU facade's host cost per step, at this run's GPU count and at 8 (host-only)
-            "inprocess_facade": [facade_overhead(max(2, world)), facade_overhead(8)],
-            "roofline": dominant,
-            "roofline_bp_angle": roofs.get(K_BP_NAME),
-            "roofline_fp_angle": roofs.get(K_FP_NAME),
-            # the TV descent: a norm pass + a recompute-and-update pass per inner iteration (gradient never stored); these two
-            # are about half instruction-bound, their launches overlap the data distance on the second stream
-            "roofline_tv_norm": roofs.get(K_TVN_NAME),
-            "roofline_tv_update": roofs.get(K_TVU_NAME),
+            "full": bool(args.full),
         }
-        if world == 1 and comm is None and not args.quick:
+        if dumped is not None:
+            out["outputs_dumped"] = dumped
+        if args.full:
+            out.update({
+                # the data-INDEPENDENT figure (k_sart_tile storing every voxel; the headline skips stores of unchanged 256-byte pieces,
+                # which the zero background of the synthetic phantom favours): null when the option was forced on the command line
+                # (round 5, resident sweep: every voxel is loaded and stored once per sweep whatever the data -- the headline IS that figure)
+                "ms_per_step_every_voxel_stored": (el / args.steps * 1e3 if resident else None) if el_all is None else el_all * 1e3,
+                "store_skipping": None if el_all is None else {
+                    "ms_per_step_with_every_voxel_stored": el_all * 1e3,
+                    "note": "k_sart_tile (in place) skips the store of 256-byte pieces whose bits did not change; bit-identical results; the "
+                            "gain depends on the data (zero background of the synthetic phantom); --opt sart_skip_same=0 times the other form"},
+                # N > 1 (and --force-dist): what the run itself can prove about its communication
+                "comm": comm_record,
+                # the plain-process multi-GPU facade's host cost per step, at this run's GPU count and at 8 (host-only)
+                "inprocess_facade": [facade_overhead(max(2, world)), facade_overhead(8)],
+                "roofline": dominant,
+                "roofline_bp_angle": roofs.get(K_BP_NAME),
+                "roofline_fp_angle": roofs.get(K_FP_NAME),
+                # the TV descent: a norm pass + a recompute-and-update pass per inner iteration (gradient never stored); these two
+                # are about half instruction-bound, their launches overlap the data distance on the second stream
+                "roofline_tv_norm": roofs.get(K_TVN_NAME),
+                "roofline_tv_update": roofs.get(K_TVU_NAME),
+            })
+        if args.full and world == 1 and comm is None and not args.quick:
             del t, log
             t = log = None
             out["secondary"] = secondary_configs()

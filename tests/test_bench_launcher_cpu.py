@@ -78,3 +78,62 @@ def test_roofline_record_of_the_resident_sweep_is_a_roofline_record():
     assert abs(r["hbm"]["frac_on_strictly_algorithmic_bytes"] - 0.034) < 0.002
     assert bench.fracs_above_one({"roofline": r, "x": [{"frac": 0.5}]}) == []
     assert bench.fracs_above_one({"a": {"frac": 1.2}, "b": [{"lds_frac": 3}]}) == [{"key": "a.frac", "value": 1.2}, {"key": "b[0].lds_frac", "value": 3}]
+
+
+def _load_bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_plain_run_is_the_headline_only_and_full_adds_the_rest():
+    """A plain run prints the headline; what else the benchmark measures (rooflines, store skipping, facade cost, the sharded
+    record) appears with --full only, and the headline's keys say the same in both."""
+    plain = run_bench("--gpus", "2", "--nslice", "6")
+    full = run_bench("--gpus", "2", "--nslice", "6", "--full")
+    extras = {"inprocess_facade", "roofline", "roofline_tv_norm", "store_skipping", "comm", "ms_per_step_every_voxel_stored"}
+    assert plain["full"] is False and not extras & set(plain)
+    assert full["full"] is True and extras <= set(full)
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps"):
+        assert plain[k] == full[k]
+    assert plain["ms_per_step"] > 0 and full["ms_per_step"] > 0
+
+
+def test_dump_outputs_hold_what_the_last_timed_step_computed(tmp_path):
+    """--dump-outputs DIR: float32 / float64 .npy files, under 64 MB, equal from run to run with the same arguments (seeded
+    inputs) and across rank counts (the whole volume is gathered); --steps sets how many steps the outputs have seen."""
+    import numpy as np
+    a = run_bench("--gpus", "2", "--nslice", "6", "--dump-outputs", str(tmp_path / "a"))
+    a2 = run_bench("--gpus", "2", "--nslice", "6", "--dump-outputs", str(tmp_path / "a2"))
+    b = run_bench("--gpus", "3", "--nslice", "6", "--dump-outputs", str(tmp_path / "b"))
+    c = run_bench("--gpus", "2", "--nslice", "6", "--steps", "3", "--dump-outputs", str(tmp_path / "c"))
+    assert c["steps"] == 3
+    names = sorted(f[:-4] for f in os.listdir(tmp_path / "a"))
+    assert names == a["outputs_dumped"] == ["final_dd", "final_tv", "recon"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 << 20
+    load = lambda d, n: np.load(tmp_path / d / (n + ".npy"))  # noqa: E731
+    assert load("a", "recon").dtype == np.float32 and load("a", "recon").shape == (6, 16, 16)
+    assert load("a", "final_dd").dtype == np.float64 and load("a", "final_dd")[0] == a["final_dd"]
+    assert load("a", "final_tv")[0] == a["final_tv"]
+    for n in names:
+        assert np.array_equal(load("a", n), load("a2", n))
+        assert np.allclose(load("a", n), load("b", n), rtol=1e-5, atol=1e-6)
+    assert not np.array_equal(load("a", "recon"), load("c", "recon"))
+
+
+def test_dump_of_a_large_volume_is_a_fixed_sample_under_64_mb(tmp_path):
+    """A reconstruction above 32 MiB is written as a seeded voxel sample plus whole slices: the same voxels every time."""
+    import numpy as np
+    bench = _load_bench()
+    vol = np.random.default_rng(3).random((520, 128, 128), dtype=np.float32)
+    for d in ("x", "y"):
+        assert bench.dump_outputs(str(tmp_path / d), vol, 0.5, 2.0) == ["final_dd", "final_tv", "recon_sample", "recon_slices"]
+    assert sum(os.path.getsize(tmp_path / "x" / f) for f in os.listdir(tmp_path / "x")) <= 64 << 20
+    sample, slices = np.load(tmp_path / "x" / "recon_sample.npy"), np.load(tmp_path / "x" / "recon_slices.npy")
+    assert sample.dtype == slices.dtype == np.float32 and 0 < sample.size <= 1 << 22
+    assert slices.shape == (8, 128, 128) and np.array_equal(slices[0], vol[0]) and np.array_equal(slices[-1], vol[-1])
+    assert np.array_equal(sample, np.load(tmp_path / "y" / "recon_sample.npy"))
+    idx = np.unique(np.random.default_rng(bench.DUMP_SEED).integers(0, vol.size, bench.DUMP_SAMPLE))     # the documented rule
+    assert np.array_equal(sample, vol.ravel()[idx])

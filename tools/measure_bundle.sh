@@ -1,10 +1,10 @@
 # Measurement bundle of a round (tools/measure_bundle.sh r03) (run on the GPU box through gpurun): bench line, rocprofv3 kernel stats of the same
 # command, PMC traffic passes (FETCH_SIZE / WRITE_SIZE in separate runs, no tracing domains besides the kernel trace).
 R=$GRAFT_REPO_ROOT; TAG=${1:-r03}; O=$R/gpurun_out/$TAG; mkdir -p $O
-cd $R && python3 bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err   # the driver's command
+cd $R && python3 bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err   # the whole benchmark record
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --quick > $O/bench_trace.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_full -- python3 $R/bench.py --no-cpu-baseline > $O/bench_trace_full.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_full -- python3 $R/bench.py --full --no-cpu-baseline > $O/bench_trace_full.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_fista -- python3 $R/tools/run_config.py --alg fista --iters 5 > $O/fista.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_sirt -- python3 $R/tools/run_config.py --alg sirt --iters 10 > $O/sirt.log 2>&1
 for grp in FETCH_SIZE WRITE_SIZE; do rocprofv3 --pmc $grp --output-format csv -d $O/pmc_$grp -- python3 $R/bench.py --steps 1 --warmup 0 --quick > $O/pmc_$grp.log 2>&1; done

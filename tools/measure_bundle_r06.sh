@@ -2,7 +2,7 @@
 # stats of the same command and of the FISTA / SIRT / sharded runs, PMC traffic passes (FETCH_SIZE / WRITE_SIZE in separate runs, no tracing domains
 # besides the kernel trace).  Summaries land in gpurun_out/r06/; copy what is to be judged into profiles/.
 R=$GRAFT_REPO_ROOT; TAG=r06; O=$R/gpurun_out/$TAG; mkdir -p $O
-cd $R && python3 bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err   # the driver's command
+cd $R && python3 bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err   # the whole benchmark record
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --quick --steps 20 --warmup 5 > $O/bench_trace.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_fista -- python3 $R/tools/run_config.py --alg fista --iters 5 > $O/fista.log 2>&1
