@@ -330,6 +330,8 @@ int tomo_mm_update(tomo_engine *ce, const int32_t *xvols, const int32_t *uvols, 
 int tomo_set_option(tomo_engine *e, const char *name, int value);
 /* read back a switch, or a fact about the engine: "fp_strip", "fp_list", "fp_tile", "bp_tile", "bp_list", "fgp_pair", "fp_reuse", "sart_tile", and
  * "fp_list_ready" (1: the list form of the strips was built),
+ * "art_chain_ready" (1: every pixel's two rays of an angle are neighbours, so a natural-order ART sweep runs as the chain, k_art_chain,
+ * where "art_chain" = 1; 0: it runs row by row, k_art),
  * "bp_list_ready" (1: the entry lists of k_bp_list were built: every tile's ray windows fit and there are at most 192 angles),
  * "fp_strip_ready" (1: the sheared-strip tables were built at creation -- by the slab-size rule or TOMO_FP_STRIP=1 -- so
  * "fp_strip" = 1 takes effect), "fp_strip_slots" (accumulator slots per lane group the strip kernel runs with),
