@@ -19,6 +19,10 @@ Bounds (u = 2^-24, gamma_m = m u / (1 - m u)):
   clamped values obey the same bound as the values before it.
 * SART sweep, ``tv_gd``, FGP.  Sequential: no cheap a-priori bound.  The float32 oracle's own error is the yardstick:
   ``|hip - f64| <= 4 max_slice |oracle - f64| + 8 u |f64|`` per element (``seq_bound``).
+* FP epilogues (``Matrix.residual``, ``data_distance``, ``poisson``), the scalar reductions (``sqdiff``, ``l1``, ``tv_value``,
+  ``tv_gnorm``), the fusion steps (``mm_model``, ``mm_update``) and the host's Lipschitz constants: first-order worst-case bounds,
+  stated with each function.  Those built on device transcendentals use ``LOGF_ULP``, ``C_EXP`` and ``C_LOG``, which are
+  assumptions about the device's logf / exp2f / log2f, not measurements.  ``proj_max`` / ``proj_scale`` are exact.
 """
 import numpy as np
 
@@ -26,6 +30,23 @@ U = 2.0 ** -24
 EXTRA_SUMS = 16          # partial sums and epilogue operations a form may add to a row's / column's entry sums
 TYPICAL_FLOOR = 0.25     # in units of u (|A||x|)_i: the RMS a kernel may always have
 SAFETY = 1.5             # first-order propagation of the SIRT-type bound: room for the second-order terms
+EPS_POISSON = float(np.float32(0.1))   # the float32 eps of the Poisson epilogue ((a - b)/(a + eps), log(a + eps))
+# Accuracy ASSUMED of the device's float32 transcendentals, in units of u of the result (not measured here: the GPU tests confirm
+# that the kernels stay inside the bounds built on them, and print the worst ratio of error to bound they saw).
+LOGF_ULP = 2.0           # logf
+C_EXP = 2.0              # exp2f
+C_LOG = 2.0              # log2f
+TINY = 2.0 ** -149       # absolute floor of a result that may be subnormal (or flushed to 0)
+
+
+def DSUM(n):
+    """Relative error of a sum of n non-negative binary64 terms in any order (the double accumulations of the reductions)."""
+    return n * 2.0 ** -53 * 1.01
+
+
+def POW_REL(t):
+    """Relative error of exp2f(t') for t' = g * log2f(x) = t (1 + (1 + C_LOG) u): (C_EXP + ln2 (1 + C_LOG) |t|) u."""
+    return (C_EXP + np.log(2.0) * (1.0 + C_LOG) * np.abs(t)) * U
 
 
 def gamma(m):
@@ -177,6 +198,72 @@ class Matrix:
         cw = float(np.float32(np.float32(beta) / np.float32(self.nrow)))
         return self.sirt_step(x, b, self.rowinner, cw, gamma(self.row_nnz + 2), 2 * U)
 
+    # ---- FP epilogues (k_fp_rows, k_fp_rows_g, k_fp_tile_reduce, k_sino_resid) -------------------------------------------------------
+    def residual(self, x, b, mode):
+        """The residual epilogues, with their bounds (e = the FP bound of A x, d = b - A x):
+
+        * "resid"  ``b - A x``: ``e (1 + u) + u |d|`` (one rounding of the difference).
+        * "norm"   ``(b - A x) / rowsum``, 0 where rowsum = 0 (exactly): ``(e + u |d|) / rowsum + |r| (gamma(row_nnz + 2) + 2u)``
+          (the float32 row sum the kernel divides by, and the division).
+        * "mul"    ``(b - A x) * rowinner`` (Cimmino): ``(e + u |d|) rowinner + |r| (gamma(row_nnz + 2) + 2u)``."""
+        x = np.asarray(x, np.float64)
+        b = np.asarray(b, np.float64).reshape(len(x), self.nrow)
+        y, ey, _ = self.fp_bound(x)
+        d = b - y
+        ed = ey * (1 + U) + U * np.abs(d)
+        if mode == "resid":
+            return d, ed
+        wrel = gamma(self.row_nnz + 2)[None] + 2 * U
+        if mode == "norm":
+            ok = self.rowsum > 0
+            rw = np.where(ok, 1.0 / np.where(ok, self.rowsum, 1), 0.0)[None]
+        elif mode == "mul":
+            rw = self.rowinner[None]
+        else:
+            raise ValueError(mode)
+        r = d * rw
+        return r, ed * rw + np.abs(r) * wrel
+
+    def data_distance(self, x, b, yb=None):
+        """FP_DD: (G = A x, its FP bound, S_DD = sum (A x - b)^2, its bound).  Per term d = fl(acc - b) (error e = e_fp + u |d|), a
+        float32 square, a double sum: ``sum(2 |d| e + e^2 + 3u d^2)`` plus the double summation.  ``yb``: as for ``poisson``."""
+        y, ey = yb if yb is not None else self.fp_bound(x)[:2]
+        b = np.asarray(b, np.float64).reshape(y.shape)
+        d = y - b
+        e = ey * (1 + U) + U * np.abs(d)
+        s = float(np.sum(d * d))
+        return y, ey, s, float(np.sum(2 * np.abs(d) * e + e * e + 3 * U * d * d)) + DSUM(d.size) * s
+
+    def poisson(self, x, b, yb=None):
+        """FP_POISSON (multimodal.cpp:284-292; eps = ``EPS_POISSON``, b >= 0, A x > -eps):
+
+        * residual ``(a - b)/(a + eps)``: the FP error e_a times ``|d/da| = |eps + b|/(a + eps)^2``, plus three roundings
+          (difference, sum, quotient), times ``SAFETY``;
+        * cost ``sum(a - b log(a + eps))``: per term ``|1 - b/(a + eps)| e_a + |b log(a + eps)| LOGF_ULP u + u |b|`` (the rounded
+          a + eps) ``+ u (|a| + |b log|)`` (product and difference), times ``SAFETY``, plus the double summation.
+
+        Returns (residual, its bound, cost, its bound).  ``yb = (A x, its FP bound)`` in place of x: a projection already in hand."""
+        a, ea = yb if yb is not None else self.fp_bound(x)[:2]
+        b = np.asarray(b, np.float64).reshape(a.shape)
+        den = a + EPS_POISSON
+        r = (a - b) / den
+        er = SAFETY * (ea * np.abs(EPS_POISSON + b) / den ** 2 + 3 * U * np.abs(r))
+        lg = b * np.log(den)
+        cost = float(np.sum(a - lg))
+        ec = SAFETY * (np.abs(1 - b / den) * ea + np.abs(lg) * LOGF_ULP * U + U * np.abs(b) + U * (np.abs(a) + np.abs(lg)))
+        return r, er, cost, float(np.sum(ec)) + DSUM(a.size) * float(np.sum(np.abs(a) + np.abs(lg)))
+
+    # ---- the host's Lipschitz constants (sysmat.cpp) --------------------------------------------------------------------------------
+    def lipschitz(self, cimmino=False):
+        """``max_p (A^T A 1)_p`` (or ``max_p (A^T M A 1)_p``, M = diag(|A_i|^2)) in binary64 and a bound of the float32 host value:
+        every term is positive, each a product of float32 row sums (gamma(row_nnz)) and weights summed over a column, so
+        ``gamma(max row_nnz + col_nnz + 4)`` relative (``+ max row_nnz`` more for M)."""
+        t = self.rowsum * (self.rowinner if cimmino else 1.0)
+        v = np.bincount(self.cols, self.vals * t[self.rows], self.ncol)
+        p = int(np.argmax(v))
+        m = int(self.row_nnz.max()) * (2 if cimmino else 1) + int(self.col_nnz.max()) + 4
+        return float(v[p]), float(gamma(m) * v[p])
+
     # ---- SART sweep ---------------------------------------------------------------------------------------------------------------
     def sart(self, x, b, beta, order=None, nsweep=1):
         """SART sweeps in binary64 with the formula of ``orc_sart``: per angle i (in ``order``), r_j = (b_j - A_j x) / (A_j 1) over its
@@ -236,24 +323,44 @@ def _shift(a, axis, d, wrong_face=None):
     return s
 
 
-def tv_gd(x, ng, dPOCS, eps, wrong_face=None):
-    """``ng`` steps x -= dPOCS g / ||g|| of the TV gradient of ctvlib.cpp:431-447 (periodic in all three axes), then the clamp at
-    0 -- in binary64 (the formula of ``orc_tv_gd_f64``).  ``wrong_face``: see ``_shift``."""
-    v = np.array(x, np.float64)
+def tv_grad(v, eps, wrong_face=None):
+    """The TV gradient of ctvlib.cpp:431-447 (periodic in all three axes) in binary64, and a first-order bound of a float32 kernel's
+    error in it per element: every difference, square, sum, sqrtf and division of one of the four quotients n / d rounds once,
+    so ``|dn| <= gamma(3) (sum of |differences|)``, ``|dd| <= gamma(5) d`` (eps + three squares, the root) and one division:
+    ``|d(n/d)| <= (|dn| + gamma(6) |n|) / d``.  ``wrong_face``: see ``_shift``."""
+    v = np.asarray(v, np.float64)
 
     def S(a, ax, d):
         return _shift(a, ax, d, wrong_face)
 
     def D(c, a1, a2, a3):
         return np.sqrt(eps + (c - a1) ** 2 + (c - a2) ** 2 + (c - a3) ** 2)
+    c = v
+    xp, yp, zp = S(v, 0, 1), S(v, 1, 1), S(v, 2, 1)
+    xm, ym, zm = S(v, 0, -1), S(v, 1, -1), S(v, 2, -1)
+    terms = [((c - xp) + (c - yp) + (c - zp), np.abs(c - xp) + np.abs(c - yp) + np.abs(c - zp), D(c, xp, yp, zp)),
+             (c - xm, np.abs(c - xm), D(xm, c, S(xm, 1, 1), S(xm, 2, 1))),
+             (c - ym, np.abs(c - ym), D(ym, S(ym, 0, 1), c, S(ym, 2, 1))),
+             (c - zm, np.abs(c - zm), D(zm, S(zm, 0, 1), S(zm, 1, 1), c))]
+    g = sum(n / d for n, _, d in terms)
+    eg = sum((gamma(3) * a + gamma(6) * np.abs(n)) / d for n, a, d in terms) + gamma(4) * sum(np.abs(n) / d for n, _, d in terms)
+    return g, eg
+
+
+def tv_gnorm(x, eps, wrong_face=None):
+    """S_GNORM: sum g^2 of the TV gradient of ``x`` (float32 g squared in float32, summed in double), with its bound
+    ``sum(2 |g| e_g + e_g^2 + u g^2)`` plus the double summation."""
+    g, eg = tv_grad(np.asarray(x, np.float64), float(np.float32(eps)), wrong_face)
+    ref = float(np.sum(g * g))
+    return ref, float(np.sum(2 * np.abs(g) * eg + eg * eg + U * g * g)) + DSUM(g.size) * ref
+
+
+def tv_gd(x, ng, dPOCS, eps, wrong_face=None):
+    """``ng`` steps x -= dPOCS g / ||g|| of the TV gradient of ctvlib.cpp:431-447 (periodic in all three axes), then the clamp at
+    0 -- in binary64 (the formula of ``orc_tv_gd_f64``).  ``wrong_face``: see ``_shift``."""
+    v = np.array(x, np.float64)
     for _ in range(int(ng)):
-        c = v
-        xp, yp, zp = S(v, 0, 1), S(v, 1, 1), S(v, 2, 1)
-        xm, ym, zm = S(v, 0, -1), S(v, 1, -1), S(v, 2, -1)
-        g = (3 * c - xp - yp - zp) / D(c, xp, yp, zp)
-        g += (c - xm) / D(xm, c, S(xm, 1, 1), S(xm, 2, 1))
-        g += (c - ym) / D(ym, S(ym, 0, 1), c, S(ym, 2, 1))
-        g += (c - zm) / D(zm, S(zm, 0, 1), S(zm, 1, 1), c)
+        g, _ = tv_grad(v, eps, wrong_face)
         v = v - (float(dPOCS) / np.sqrt(np.sum(g * g))) * g
     return np.maximum(v, 0.0)
 
@@ -285,6 +392,130 @@ def tv_fgp(x, iters, lam, wrong_face=None):
         sc = np.where(den > 1.0, 1.0 / np.sqrt(np.where(den > 1.0, den, 1.0)), 1.0)
         P = [q * sc for q in Q]
     return D if iters > 0 else np.zeros_like(f)
+
+
+# ---- scalar reductions (k_sqdiff, k_l1, k_tv_value and the TV value of the gradient kernels; grid-stride, summed in double) ------
+def sqdiff(a, b):
+    """S_DIFF / S_RMSE: sum (a - b)^2; per term a float32 difference and a float32 square (3u), then the double summation."""
+    d = np.asarray(a, np.float64) - np.asarray(b, np.float64)
+    s = float(np.sum(d * d))
+    return s, 3 * U * s * 1.01 + DSUM(d.size) * s
+
+
+def l1(a):
+    """S_L1: sum |a|; the terms are exact, only the double summation rounds."""
+    s = float(np.sum(np.abs(np.asarray(a, np.float64))))
+    return s, DSUM(np.size(a)) * s
+
+
+def tv_value(x, eps, wrong_face=None):
+    """S_TV: sum sqrtf(eps + (c - x_ip)^2 + (c - x_jp)^2 + (c - x_kp)^2), periodic in all three axes (``orc_tv``); eps is the
+    float32 value.  Per term: three rounded differences and squares, three additions and the root: ``gamma(6)`` relative; then the
+    double summation.  ``wrong_face``: see ``_shift``."""
+    v = np.asarray(x, np.float64)
+    eps = float(np.float32(eps))
+    c = v
+    t = np.sqrt(eps + sum((c - _shift(v, ax, 1, wrong_face)) ** 2 for ax in range(3)))
+    s = float(np.sum(t))
+    return s, float(gamma(6)) * s + DSUM(t.size) * s
+
+
+# ---- the fusion kernels (k_mm_model / k_mm_update: multimodal.cpp:425-438, 277-304) ------------------------------------------------
+def _pow(x, g):
+    """x^g in binary64 with the kernel's rules at 0 (0^0 = 1, 0^g = 0 for g > 0, inf for g < 0) and its per-element bound: exact
+    at x == 0 and where g == 1; else ``POW_REL(g log2 |x|) |x^g| + TINY``.  x < 0 takes powf (numpy's value: NaN unless g is an
+    integer), under the same allowance."""
+    x = np.asarray(x, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p = np.power(x, g)
+        p = np.where(x == 0, 1.0 if g == 0 else (0.0 if g > 0 else np.inf), p)
+        t = g * np.log2(np.where(x != 0, np.abs(x), 1.0))
+    e = np.where(x == 0, 0.0, POW_REL(t) * np.abs(np.where(np.isfinite(p), p, 0)) + TINY)
+    return p, e
+
+
+def mm_model(xs, w, g):
+    """``sum_e w_e x_e^g``.  g == 1: the plain float32 sum, ``gamma(nel + 1) sum |w_e x_e|``.  Otherwise each power carries its
+    ``_pow`` allowance times |w_e|, plus ``gamma(nel + 1) sum |w_e x_e^g|``.  Returns (model, bound)."""
+    g = float(np.float32(g))
+    w = np.asarray(w, np.float32).astype(np.float64)
+    acc, mag, err = 0.0, 0.0, 0.0
+    for e in range(len(xs)):
+        p, ep = (np.asarray(xs[e], np.float64), 0.0) if g == 1.0 else _pow(xs[e], g)
+        acc = acc + w[e] * p
+        mag = mag + np.abs(w[e] * p)
+        err = err + np.abs(w[e]) * ep
+    with np.errstate(invalid="ignore"):
+        return acc, err + gamma(len(xs) + 1) * mag + 2 * len(xs) * TINY     # (products and sums that underflow)
+
+
+def mm_update(xs, us, w, g, lamC_over_L, lamH, upd=None, model=None):
+    """``x_e <- max(0, x_e - (c u_e - lamH g x_e^(g-1) w_e (upd - model)))``, c = lamC_over_L (float32 values), per element e.
+    lamH == 0 is poisson_ML (multimodal.cpp:277-304): ``max(0, x_e - c u_e)``, bound ``u |c u_e| + u |x_e - c u_e|``.  Otherwise the
+    HAADF term H carries ``(POW_REL + 5u) |H|`` (difference, two products, g *, the power; TINY for a subnormal power) and the rest
+    one rounding per operation, times ``SAFETY`` (and 8 ``TINY`` for products that underflow).  At x_e == 0 with g < 1 the power is inf: the engine's value there is +inf where
+    w_e (upd - model) > 0 and 0 elsewhere (inf * 0 = NaN, and fmaxf(NaN, 0) = 0); those elements are exact (bound 0).
+    Returns a list of (new x_e, bound)."""
+    g = float(np.float32(g))
+    c, lamH = float(np.float32(lamC_over_L)), float(np.float32(lamH))
+    w = np.asarray(w, np.float32).astype(np.float64)
+    out = []
+    D = None if lamH == 0 else np.asarray(upd, np.float64) - np.asarray(model, np.float64)
+    for e in range(len(xs)):
+        x, u = np.asarray(xs[e], np.float64), np.asarray(us[e], np.float64)
+        A = c * u
+        if lamH == 0:
+            v = x - A
+            bound = U * np.abs(A) + U * np.abs(v) * 1.01 + 2 * TINY
+            out.append((np.maximum(v, 0.0), bound))
+            continue
+        wd = w[e] * D
+        if g == 1.0:
+            H, eH = lamH * wd, 3 * U * np.abs(lamH * wd)
+            special = np.zeros(x.shape, bool)
+        else:
+            p, ep = _pow(x, g - 1.0)
+            special = ~np.isfinite(p)
+            with np.errstate(invalid="ignore"):
+                H = np.where(special, 0.0, lamH * g * p * wd)
+                eH = np.where(special, 0.0, np.abs(H) * 5 * U + lamH * abs(g) * ep * np.abs(wd))
+        v = x - (A - H)
+        bound = SAFETY * (eH + U * np.abs(A) + U * np.abs(A - H) + U * np.abs(v)) + 8 * TINY
+        new = np.maximum(v, 0.0)
+        new = np.where(special, np.where(wd > 0, np.inf, 0.0), new)
+        out.append((new, np.where(special, 0.0, bound)))
+    return out
+
+
+# ---- per-projection max / scale (k_proj_max, k_proj_scale: multimodal.cpp:312-328) -------------------------------------------------
+def proj_max(sino, P, N):
+    """Max over the rays and slices of each projection of a (nslice, P N) sinogram: exact (a float32 max)."""
+    s = np.asarray(sino, np.float32).reshape(len(sino), P, N)
+    return s.max(axis=(0, 2))
+
+
+def proj_scale(sino, P, N, div, mul):
+    """``(b / div_p) * mul_p`` per projection, each operation correctly rounded in float32: exact."""
+    s = np.asarray(sino, np.float32).reshape(len(sino), P, N)
+    d = np.asarray(div, np.float32)[None, :, None]
+    m = np.asarray(mul, np.float32)[None, :, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return ((s / d).astype(np.float32) * m).astype(np.float32).reshape(len(sino), P * N)
+
+
+def assert_scalar(name, got, ref, bound):
+    """|got - ref| <= bound for one scalar."""
+    if not abs(float(got) - float(ref)) <= bound:
+        raise AssertionError(f"{name}: got {float(got)!r}, f64 {float(ref)!r}: error {abs(float(got) - float(ref)):.3e} > bound {bound:.3e}")
+
+
+def ratio(got, ref, bound):
+    """The largest |got - ref| / bound over the elements with a bound > 0 (how close a kernel came to its bound)."""
+    got = np.asarray(got, np.float64)
+    ref = np.asarray(ref, np.float64).reshape(got.shape)
+    bound = np.broadcast_to(np.asarray(bound, np.float64), got.shape)
+    m = (bound > 0) & np.isfinite(ref)
+    return float(np.max(np.abs(got[m] - ref[m]) / bound[m])) if m.any() else 0.0
 
 
 # ---- checks -------------------------------------------------------------------------------------------------------------------------
@@ -348,3 +579,23 @@ def signed_sino(nx, nrow, seed=0):
     rng = np.random.default_rng(seed)
     off = (np.arange(nx) % 5) * 0.1 - 0.2
     return (rng.uniform(-1.0, 1.0, (nx, nrow)) + off[:, None]).astype(np.float32)
+
+
+def sentinel_positions(nx, n):
+    """(slice, y, z) of the reduction sentinels: the first element, the last real element of the last slice, the first element of the
+    second 64-slice chunk (when there is one) and an element in lane 3 of a float4 group (slice 3 of a middle pixel)."""
+    pos = [(0, 0, 0), (nx - 1, n - 1, n - 1)]
+    if nx > 64:
+        pos.append((64, 0, 0))
+    if nx > 3:
+        pos.append((3, n // 2, n // 3))
+    return sorted(set(pos))
+
+
+def with_sentinels(x, factor=64.0):
+    """A copy of volume x with its ``sentinel_positions`` values multiplied by ``factor``: dropping or double-counting any one of them
+    moves a reduction far outside its bound."""
+    x = np.array(x, np.float32)
+    for p in sentinel_positions(*x.shape[:2]):
+        x[p] *= np.float32(factor)
+    return x

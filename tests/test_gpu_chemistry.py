@@ -39,8 +39,10 @@ def make_case(N=32, Nx=6, Ph=9, Pc=7, Nel=2, gamma=1.6, seed=0):
     return dev, ref, gt
 
 
-@pytest.mark.parametrize("gamma", [1.0, 1.6])
+@pytest.mark.parametrize("gamma", [1.0, 1.6, 0.5])
 def test_poisson_ml_then_data_fusion(gpu, gamma):
+    """At gamma < 1 only the Poisson-ML half: the fusion step's x^(gamma-1) is infinite at the voxels Poisson-ML leaves at 0, where
+    the reference's own update is inf or NaN (tests/test_gpu_elementwise_scalars.py states the engine's rule there)."""
     dev, ref, gt = make_case(gamma=gamma)
     assert abs(dev.L_Aps - float(ref.L_Aps)) <= 1e-6 * dev.L_Aps
     for it in range(5):
@@ -48,6 +50,8 @@ def test_poisson_ml_then_data_fusion(gpu, gamma):
         assert abs(c_dev - c_ref) <= 2e-5 * abs(c_ref), it
     assert rel_l2(dev.get_volume(), ref.recon) < TOL
     assert abs(dev.data_distance() - ref.data_distance()) <= 1e-5 * ref.data_distance()
+    if gamma < 1:
+        return
     dev.rescale_tomograms(10)
     ref.rescale_tomograms(10)
     dev.rescale_projections()

@@ -220,3 +220,336 @@ def test_tv_yardsticks_catch_a_wrong_boundary_rule_on_one_face(axis, side):
     ref64.assert_seq("fgp", orc.recon, orc.recon, g64)
     with pytest.raises(AssertionError):
         ref64.assert_seq("fgp", ref64.tv_fgp(x, 2, 0.05, wrong_face=(axis, side)).astype(np.float32), orc.recon, g64)
+
+
+# ---- FP epilogues, scalar reductions, fusion steps -------------------------------------------------------------------------------------
+F32 = np.float32
+
+
+def _orc_fp(M, x):
+    """The float32 oracle's A x."""
+    orc = oracle.ctvlib(len(x), M.N, M.P)
+    orc.A = oracle.CSR(M.nrow, M.ncol, *M.csr())
+    orc.original_volume = np.ascontiguousarray(x, F32)
+    orc.create_projections()
+    return orc, orc.b.copy()
+
+
+def _orc_epilogues(M, x, b):
+    """The five epilogues in float32 from the oracle's projection (the kernels' expressions)."""
+    orc, a = _orc_fp(M, x)
+    rs32 = _orc_fp(M, np.ones((1, M.N, M.N), F32))[1][0]          # A 1 in float32
+    orc.row_inner_product()
+    d = (b - a).astype(F32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        norm = np.where(rs32 > 0, d / rs32, F32(0)).astype(F32)
+    mul = (d * orc.innerProduct).astype(F32)
+    dd = float(np.sum(((a - b).astype(F32) ** 2).astype(np.float64)))
+    eps = F32(0.1)
+    pr = ((a - b) / (a + eps)).astype(F32)
+    cost = float(np.sum((a - b * np.log(a + eps, dtype=F32)).astype(np.float64)))
+    return dict(a=a, resid=d, norm=norm, mul=mul, dd=dd, pr=pr, cost=cost, rs32=rs32)
+
+
+def _poisson_data(M, nx, seed):
+    b = np.abs(ref64.signed_sino(nx, M.nrow, seed=seed)) * F32(M.N / 4)
+    b[:, ::7] = 0                                                   # rows where b is 0
+    return b.astype(F32)
+
+
+@pytest.mark.parametrize("name,N,nx", CASES, ids=[c[0] for c in CASES])
+def test_oracle_within_epilogue_bounds(name, N, nx):
+    M, _ = _setup(name, N, nx)
+    x = ref64.dense_volume(nx, N, seed=12)
+    b = ref64.signed_sino(nx, M.nrow, seed=13)
+    o = _orc_epilogues(M, x, b)
+    for mode, key in (("resid", "resid"), ("norm", "norm"), ("mul", "mul")):
+        ref, bound = M.residual(x, b, mode)
+        ref64.assert_within(mode, o[key], ref, bound)
+    zero = M.rowsum == 0
+    assert np.all(o["norm"][:, zero] == 0)
+    g, eg, s, es = M.data_distance(x, b)
+    ref64.assert_within("G", o["a"], g, eg)
+    ref64.assert_scalar("S_DD", o["dd"], s, es)
+    bp = _poisson_data(M, nx, 14)
+    o = _orc_epilogues(M, x, bp)
+    r, er, c, ec = M.poisson(x, bp)
+    ref64.assert_within("poisson residual", o["pr"], r, er)
+    ref64.assert_scalar("S_COST", o["cost"], c, ec)
+
+
+@pytest.fixture(scope="module")
+def epi_case():
+    M, _ = _setup("lin70", 32, 3)
+    x = ref64.dense_volume(3, 32, seed=15)
+    b = ref64.signed_sino(3, M.nrow, seed=16)
+    return M, x, b, _orc_epilogues(M, x, b)
+
+
+EPI_CORRUPT = [("resid", "sign_flip"), ("norm", "sign_flip"), ("mul", "sign_flip"), ("norm", "neighbour_rowsum"),
+               ("mul", "neighbour_rowsum")]
+
+
+@pytest.mark.parametrize("mode,kind", EPI_CORRUPT, ids=[f"{m}-{k}" for m, k in EPI_CORRUPT])
+def test_epilogue_bounds_catch_corruption(epi_case, mode, kind):
+    M, x, b, o = epi_case
+    ref, bound = M.residual(x, b, mode)
+    good = o[mode]
+    ref64.assert_within(mode, good, ref, bound)
+    bad = good.copy()
+    if kind == "sign_flip":
+        i = int(np.argmax(np.abs(good[1])))
+        bad[1, i] = -bad[1, i]
+    else:
+        f = o["rs32"] if mode == "norm" else (M.rowinner.astype(F32))
+        fn = np.roll(f, 1)                                          # the neighbouring row's factor
+        d = o["resid"]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            bad = np.where(fn > 0, d / fn, 0).astype(F32) if mode == "norm" else (d * fn).astype(F32)
+    with pytest.raises(AssertionError):
+        ref64.assert_within(mode, bad, ref, bound)
+
+
+def test_poisson_and_dd_bounds_catch_corruption(epi_case):
+    M, x, _, _ = epi_case
+    bp = _poisson_data(M, 3, 17)
+    o = _orc_epilogues(M, x, bp)
+    r, er, c, ec = M.poisson(x, bp)
+    bad = o["pr"].copy()
+    i = int(np.argmax(np.abs(bad[2])))
+    bad[2, i] = -bad[2, i]
+    with pytest.raises(AssertionError):
+        ref64.assert_within("poisson", bad, r, er)
+    a = o["a"]
+    k = int(np.argmax(a[0]))
+    term = float(a[0, k]) - float(bp[0, k]) * float(np.log(np.float64(a[0, k]) + ref64.EPS_POISSON))
+    with pytest.raises(AssertionError):                              # one term left out of the cost
+        ref64.assert_scalar("S_COST", o["cost"] - term, c, ec)
+    _, _, s, es = M.data_distance(x, bp)
+    d = (a - bp).astype(np.float64)
+    with pytest.raises(AssertionError):                              # the last real slice left out
+        ref64.assert_scalar("S_DD", o["dd"] - float(np.sum(d[-1] ** 2)), s, es)
+
+
+def _f32_sqdiff_terms(a, b):
+    return (((a - b).astype(F32)) ** 2).astype(F32).astype(np.float64)
+
+
+def _tv_terms_f32(x, eps):
+    """The float32 TV value terms of k_tv_value / orc_tv."""
+    x = np.asarray(x, F32)
+    s = (F32(eps) + ((x - np.roll(x, -1, 0)) ** 2).astype(F32)).astype(F32)
+    s = (s + ((x - np.roll(x, -1, 1)) ** 2).astype(F32)).astype(F32)
+    s = (s + ((x - np.roll(x, -1, 2)) ** 2).astype(F32)).astype(F32)
+    return np.sqrt(s).astype(np.float64)
+
+
+def _tv_grad_f32(x, eps):
+    """The TV gradient of ctvlib.cpp:431-447 evaluated in float32 (every operation rounded), the kernels' expression."""
+    x = np.asarray(x, F32)
+    eps = F32(eps)
+
+    def S(a, ax, d):
+        return np.roll(a, -d, ax)
+
+    def D(c, a1, a2, a3):
+        return np.sqrt(eps + (c - a1) * (c - a1) + (c - a2) * (c - a2) + (c - a3) * (c - a3))
+    c = x
+    xp, yp, zp = S(x, 0, 1), S(x, 1, 1), S(x, 2, 1)
+    xm, ym, zm = S(x, 0, -1), S(x, 1, -1), S(x, 2, -1)
+    g = (((c - xp) + (c - yp)) + (c - zp)) / D(c, xp, yp, zp)
+    g = g + (c - xm) / D(xm, c, S(xm, 1, 1), S(xm, 2, 1))
+    g = g + (c - ym) / D(ym, S(ym, 0, 1), c, S(ym, 2, 1))
+    g = g + (c - zm) / D(zm, S(zm, 0, 1), S(zm, 1, 1), c)
+    return g.astype(F32)
+
+
+REDUCTION_SHAPES = [(5, 12), (66, 8), (3, 9)]
+
+
+@pytest.mark.parametrize("nx,N", REDUCTION_SHAPES)
+def test_oracle_within_reduction_bounds(nx, N):
+    x = ref64.with_sentinels(ref64.dense_volume(nx, N, seed=18))
+    y = ref64.dense_volume(nx, N, seed=19)
+    s, es = ref64.sqdiff(x, y)
+    ref64.assert_scalar("S_DIFF", float(np.sum(_f32_sqdiff_terms(x, y))), s, es)
+    s, es = ref64.l1(x - F32(1.0))
+    ref64.assert_scalar("S_L1", float(np.sum(np.abs((x - F32(1.0)).astype(np.float64)))), s, es)
+    orc = oracle.ctvlib(nx, N, 1)
+    orc.tv_eps = 1e-6
+    orc.recon[:] = x
+    s, es = ref64.tv_value(x, 1e-6)
+    ref64.assert_scalar("S_TV", orc.tv(), s, es)
+    ref64.assert_scalar("S_TV", float(np.sum(_tv_terms_f32(x, 1e-6))), s, es)
+    g32 = _tv_grad_f32(x, 1e-6).astype(np.float64)
+    s, es = ref64.tv_gnorm(x, 1e-6)
+    ref64.assert_scalar("S_GNORM", float(np.sum((g32 * g32).astype(F32).astype(np.float64))), s, es)
+
+
+def test_tv_gd_still_matches_the_oracle_after_factoring_the_gradient():
+    nx, N = 4, 10
+    x = ref64.dense_volume(nx, N, seed=20)
+    orc = oracle.ctvlib(nx, N, 1)
+    orc.tv_eps = 1e-6
+    f64_c = orc.tv_gd_f64(2, 0.3, start=x)
+    t64 = ref64.tv_gd(x, 2, 0.3, 1e-6)
+    assert np.abs(t64 - f64_c).max() <= ref64.U * np.abs(t64).max()
+
+
+@pytest.mark.parametrize("kind", ["drop_float4", "drop_last_slice", "double_last_slice", "drop_sentinel_chunk2"])
+def test_reduction_bounds_catch_dropped_or_doubled_terms(kind):
+    """One float4 group (4 consecutive slices of one pixel, the volume's storage order), the last real slice, or the sentinel at the
+    start of the second 64-slice chunk, dropped from or added twice to S_DIFF, S_L1, S_TV and S_GNORM."""
+    nx, N = 66, 8
+    x = ref64.with_sentinels(ref64.dense_volume(nx, N, seed=21))
+    y = ref64.dense_volume(nx, N, seed=22)
+    terms = {"S_DIFF": (_f32_sqdiff_terms(x, y), ref64.sqdiff(x, y)),
+             "S_L1": (np.abs(x.astype(np.float64)), ref64.l1(x)),
+             "S_TV": (_tv_terms_f32(x, 1e-6), ref64.tv_value(x, 1e-6))}
+    g32 = _tv_grad_f32(x, 1e-6).astype(np.float64)
+    terms["S_GNORM"] = ((g32 * g32).astype(F32).astype(np.float64), ref64.tv_gnorm(x, 1e-6))
+    for name, (t, (s, es)) in terms.items():
+        ref64.assert_scalar(name, float(np.sum(t)), s, es)
+        if kind == "drop_float4":
+            delta = -float(np.sum(t[0:4, 0, 0]))                        # the float4 of pixel 0 holding the first sentinel
+        elif kind == "drop_last_slice":
+            delta = -float(np.sum(t[-1]))
+        elif kind == "double_last_slice":
+            delta = float(np.sum(t[-1]))
+        else:
+            delta = -float(t[64, 0, 0])
+        assert abs(delta) > 10 * es, (name, kind, delta, es)          # the sentinels keep the margin wide
+        with pytest.raises(AssertionError):
+            ref64.assert_scalar(name, float(np.sum(t)) + delta, s, es)
+
+
+def test_tv_value_catches_a_clamped_face():
+    nx, N = 6, 10
+    x = ref64.with_sentinels(ref64.dense_volume(nx, N, seed=23))
+    s, es = ref64.tv_value(x, 1e-6)
+    for axis in range(3):
+        bad, _ = ref64.tv_value(x, 1e-6, wrong_face=(axis, "hi"))
+        with pytest.raises(AssertionError):
+            ref64.assert_scalar("S_TV", bad, s, es)
+        gbad, _ = ref64.tv_gnorm(x, 1e-6, wrong_face=(axis, "hi"))
+        s2, es2 = ref64.tv_gnorm(x, 1e-6)
+        with pytest.raises(AssertionError):
+            ref64.assert_scalar("S_GNORM", gbad, s2, es2)
+
+
+# ---- fusion kernels ----------------------------------------------------------------------------------------------------------------
+def fusion_volumes(nel, shape, seed, negative=False):
+    """Per-element volumes with exact zeros, subnormals, values down to 1e-30 and up to 1e3 (and negative voxels if asked)."""
+    rng = np.random.default_rng(seed)
+    xs = []
+    for e in range(nel):
+        v = np.exp(rng.uniform(np.log(1e-3), np.log(1e3), shape)).astype(F32)
+        flat = v.reshape(-1)
+        k = flat.size
+        flat[rng.choice(k, k // 16, replace=False)] = 0
+        flat[rng.choice(k, k // 32, replace=False)] = np.exp(rng.uniform(np.log(1e-30), np.log(1e-3), k // 32)).astype(F32)
+        flat[rng.choice(k, k // 64, replace=False)] = (rng.integers(1, 2 ** 23, k // 64) * 2.0 ** -149).astype(F32)
+        flat[:4] = [0, 1.4e-45, 1e-30, 1e3]
+        if negative:
+            flat[rng.choice(k, k // 16, replace=False)] *= -1
+        xs.append(v)
+    return xs
+
+
+def _mm_model_f32(xs, w, g):
+    """oracle/multimodal.py: model()."""
+    acc = np.zeros(xs[0].shape, F32)
+    for e in range(len(xs)):
+        acc = (acc + F32(w[e]) * (xs[e] if g == 1 else np.power(xs[e], F32(g), dtype=F32))).astype(F32)
+    return acc
+
+
+def _mm_update_f32(xs, us, w, g, c, lamH, upd=None, model=None, corrupt=None):
+    """oracle/multimodal.py: the updates of data_fusion (lamH != 0) and poisson_ml (lamH == 0), in float32."""
+    out = []
+    g, c, lamH = F32(g), F32(c), F32(lamH)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        for e in range(len(xs)):
+            x, u = xs[e], us[e]
+            if lamH == 0:
+                v = (x - (c * u).astype(F32)).astype(F32)
+            else:
+                uh = (F32(w[e]) * (upd - model).astype(F32)).astype(F32)
+                if g != 1:
+                    pw = np.power(x, g if corrupt == "pow_gamma" else g - F32(1.0), dtype=F32)
+                    uh = ((g * pw).astype(F32) * uh).astype(F32)
+                v = (x - ((c * u).astype(F32) - (lamH * uh).astype(F32))).astype(F32)
+            out.append(v if corrupt == "no_clamp" else np.fmax(v, F32(0)))
+    return out
+
+
+@pytest.mark.parametrize("g", [1.0, 1.6, 2.0, 0.5])
+@pytest.mark.parametrize("nel", [1, 3, 8])
+def test_oracle_within_fusion_bounds(nel, g):
+    shape = (3, 8, 8)
+    w = np.linspace(0.3, 1.7, nel).astype(F32)
+    xs = fusion_volumes(nel, shape, seed=nel * 10, negative=(g == 2.0))
+    ref, bound = ref64.mm_model(xs, w, g)
+    ref64.assert_within("model", _mm_model_f32(xs, w, g), ref, bound)
+    xs = fusion_volumes(nel, shape, seed=nel * 10 + 1)
+    rng = np.random.default_rng(nel)
+    us = [rng.uniform(-2, 2, shape).astype(F32) for _ in range(nel)]
+    upd, model = rng.uniform(0, 3, shape).astype(F32), rng.uniform(0, 3, shape).astype(F32)
+    upd.reshape(-1)[:8] = model.reshape(-1)[:8]                       # D == 0 at a zero voxel as well
+    for lamH in (0.0, 0.7):
+        got = _mm_update_f32(xs, us, w, g, 0.05, lamH, upd, model)
+        for e, (r, b) in enumerate(ref64.mm_update(xs, us, w, g, 0.05, lamH, upd, model)):
+            fin = np.isfinite(r)
+            assert np.array_equal(got[e][~fin], r[~fin]), (e, lamH)
+            ref64.assert_within(f"update e{e} lamH {lamH}", got[e][fin], r[fin], b[fin])
+
+
+@pytest.mark.parametrize("kind", ["swap_weights", "pow_gamma", "no_clamp"])
+def test_fusion_bounds_catch_corruption(kind):
+    nel, shape, g = 3, (2, 8, 8), 1.6
+    w = np.array([0.2, 0.5, 0.9], F32)
+    xs = fusion_volumes(nel, shape, seed=5)
+    rng = np.random.default_rng(6)
+    us = [rng.uniform(-2, 2, shape).astype(F32) for _ in range(nel)]
+    upd, model = rng.uniform(0, 3, shape).astype(F32), rng.uniform(0, 3, shape).astype(F32)
+    if kind == "swap_weights":
+        ref, bound = ref64.mm_model(xs, w, g)
+        ref64.assert_within("model", _mm_model_f32(xs, w, g), ref, bound)
+        with pytest.raises(AssertionError):
+            ref64.assert_within("model", _mm_model_f32(xs, w[[1, 0, 2]], g), ref, bound)
+        return
+    refs = ref64.mm_update(xs, us, w, g, 0.05, 0.7, upd, model)
+    bad = _mm_update_f32(xs, us, w, g, 0.05, 0.7, upd, model, corrupt=kind)
+    with pytest.raises(AssertionError):
+        for e, (r, b) in enumerate(refs):
+            ref64.assert_within("update", bad[e], r, b)
+
+
+def test_proj_max_and_scale_are_exact_and_catch_the_padding():
+    """k_proj_max leaves the padding slices out: on a sinogram whose projections are all negative, a max that counted the (zero)
+    padding would return 0."""
+    P, N, nx = 4, 6, 5
+    rng = np.random.default_rng(7)
+    s = rng.uniform(-3, 2, (nx, P * N)).astype(F32)
+    s[:, N:2 * N] = -np.abs(s[:, N:2 * N]) - F32(0.5)                 # projection 1 all negative
+    m = ref64.proj_max(s, P, N)
+    assert m[1] < 0 and np.array_equal(m, s.reshape(nx, P, N).max(axis=(0, 2)))
+    padded = np.maximum(m, 0)
+    assert not np.array_equal(padded, m)
+    div, mul = m + F32(5), np.linspace(0.5, 2, P).astype(F32)
+    out = ref64.proj_scale(s, P, N, div, mul)
+    blk = (s.reshape(nx, P, N) / div[None, :, None]).astype(F32) * mul[None, :, None]
+    assert np.array_equal(out, blk.astype(F32).reshape(nx, P * N))
+
+
+@pytest.mark.parametrize("name,N", [("lin70", 32), ("axes45", 33), ("neg150", 32), ("p1_90", 16)])
+def test_oracle_lipschitz_within_bound(name, N):
+    M, orc = _setup(name, N, 1)
+    L, eL = M.lipschitz()
+    ref64.assert_scalar("lipschitz", orc.lipschits(), L, eL)
+    orc.cimminos_method()
+    L, eL = M.lipschitz(cimmino=True)
+    ref64.assert_scalar("lipschitz_cimmino", orc.lipschits(), L, eL)
+    with pytest.raises(AssertionError):                               # the second largest column instead
+        v = np.bincount(M.cols, M.vals * (M.rowsum * M.rowinner)[M.rows], M.ncol)
+        ref64.assert_scalar("lipschitz_cimmino", np.sort(v)[-2] if np.sort(v)[-2] != v.max() else v.max() * (1 - 1e-4), L, eL)

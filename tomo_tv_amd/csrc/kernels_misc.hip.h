@@ -141,9 +141,18 @@ __global__ __launch_bounds__(256) void k_mm_update(MMArgs a, const f4 *__restric
         for (int e = 0; e < a.nel; ++e) {
             f4 x = reinterpret_cast<f4 *>(a.x[e])[i];
             f4 uc = reinterpret_cast<const f4 *>(a.u[e])[i];
-            f4 uh = a.w[e] * d;                                   // Sigma^T (updateVol - modelHAADF)
-            if (a.gamma != 1.0f) uh = (a.gamma * pow4(x, a.gamma - 1.0f)) * uh;
-            f4 v = x - (lamC_over_L * uc - lamH * uh);
+            f4 v;
+            if (lamH != 0.f) {
+                f4 uh = a.w[e] * d;                               // Sigma^T (updateVol - modelHAADF)
+                if (a.gamma != 1.0f) uh = (a.gamma * pow4(x, a.gamma - 1.0f)) * uh;
+                v = x - (lamC_over_L * uc - lamH * uh);
+            } else {
+                // poisson_ML (multimodal.cpp:277-304) has no HAADF term.  Forming it anyway gave x^(gamma-1) = inf at x == 0 for
+                // gamma < 1, inf * 0 = NaN and fmaxf(NaN, 0) = 0: a zero voxel never moved.  Product and difference rounded apart,
+                // as the term-carrying path rounds them (lamH * uh == 0 there): the same bits wherever that path was finite.
+#pragma clang fp contract(off)
+                v = x - lamC_over_L * uc;
+            }
             v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
             reinterpret_cast<f4 *>(a.x[e])[i] = v;
         }
