@@ -241,6 +241,32 @@ int tomo_tv_gd_tracked(tomo_engine *e, int ng, float dPOCS, float eps, int track
 int tomo_tv_fgp(tomo_engine *e, int iters, float lambda);               /* :448-450 tv_fgp_3D; TV of input -> TOMO_S_TV */
 int tomo_tv_fgp_vol(tomo_engine *e, int vol, int iters, float lambda);  /* multimodal.cpp:497 tv_fgp_4D, one element */
 
+/* ---- Chambolle-Pock (PDHG) for  min_{x >= 0} 1/2 |Ax - b|^2 + lambda |grad x|_{2,1} ---------------------------------------
+ * The reference's unfinished counterpart is gpu/utils/regularizers/tv_chambolle.cu (in its tree, not compiled); the arithmetic
+ * here is this project's own.  Index convention x[s][y][z], the three axes alike, Neumann ends: (grad x)_a[i] = x[i + 1_a] - x[i]
+ * where i_a < n_a - 1, else 0; (div p)[i] = sum_a p_a[i] - p_a[i - 1_a] with p_a[-1] = 0 and p_a = 0 at the last index of axis a
+ * (written as 0 whatever was read), so <grad x, p> = <x, -div p> exactly.  One iteration (theta = 1 by default):
+ *     g = A xbar;  q <- (q + S (g - b)) / (1 + S);  u = A^T q;
+ *     p <- a / max(1, |a|_2 / lambda), a = p + s_grad grad xbar;  x_new = max(0, x - T (u - div p));  xbar <- x_new + theta (x_new - x)
+ * precond = 0: S = s_grad = sigma, T = tau, tau sigma (L_A + 12) <= 1 (L_A = tomo_lipschitz, 12 >= |grad|^2).  precond = 1 (diagonal,
+ * Pock-Chambolle 2011, alpha = 1): S_i = 1 / rowsum_i (0 for an empty ray), s_grad = 1/2, T_j = 1 / (colsum_j + d_j), d_j = the
+ * difference rows that touch voxel j (0..6); sigma and tau are not read.
+ * All four calls run on the engine's stream and never synchronise; they return TOMO_ERR_STATE on an engine with a communicator or
+ * whose slab is not both first and last (tomo_set_slab_edges): the slab-sharded form needs halo planes of p and xbar. */
+/* step 1 on sinogram slots (q may be TOMO_SINO_USER0 + k); tv_chambolle.cu has no data term: the dual sinogram is new here */
+int tomo_pdhg_sino_dual(tomo_engine *e, int q_sino, int g_sino, int b_sino, float sigma, int precond);
+/* step 3 as ONE fused pass over caller-named volume slots (counterpart of the dual / primal kernels sketched in tv_chambolle.cu):
+ * p lives in p_vol0 .. p_vol0 + 2 (axis s, y, z).  After the call the named slots hold the new fields, whatever buffers were swapped
+ * underneath.  slot >= 0: also sum (x_new - x)^2 -> that scalar; -1: none.  44 bytes per voxel. */
+int tomo_pdhg_tv_step(tomo_engine *e, int x_vol, int xbar_vol, int u_vol, int p_vol0, float sigma, float tau, float lambda,
+                      float theta, int precond, int slot);
+/* whole-call form (the loop tv_chambolle.cu was meant to drive): tomo_pdhg_begin sets p = 0, q = 0, xbar = RECON; tomo_pdhg runs niter
+ * iterations on RECON, YK (xbar), TEMP (u), an engine-owned dual field and dual sinogram (TOMO_SINO_R holds A xbar), which are
+ * kept across calls until the next begin.  Scalar mode: tau = ratio / sqrt(L_A + 12), sigma = 1 / (ratio sqrt(L_A + 12)).
+ * slot: as above, of the last iteration. */
+int tomo_pdhg_begin(tomo_engine *e);
+int tomo_pdhg(tomo_engine *e, int niter, float lambda, float theta, int precond, float ratio, int slot);
+
 /* ---- multimodal (ChemicalTomo) element-wise steps ---------------------------------------------------------
  * Two engines with the same slab shape on one device and stream: `ce` carries the chemical geometry and the
  * per-element tomograms, `he` the HAADF geometry, the model volume Sigma*x^gamma and the SIRT-updated model.
@@ -389,7 +415,8 @@ int tomo_sart_chain_count(tomo_engine *e, int *count);
 enum tomo_kernel_id { TOMO_K_BP_ANGLE = 0, TOMO_K_FP_ANGLE = 1, TOMO_K_TV_GRAD = 2, TOMO_K_TV_UPDATE = 3,
                       TOMO_K_FGP_OBJ = 4, TOMO_K_FGP_GRAD = 5 /* also the fused FGP iteration */, TOMO_K_SART_FUSED = 6,
                       TOMO_K_FP_TILE = 7, TOMO_K_BP_TILE = 8, TOMO_K_FP_REDUCE = 9,
-                      TOMO_K_SART_RESIDENT = 10 /* one launch = one whole SART sweep of the slab (volume-resident form) */ };
+                      TOMO_K_SART_RESIDENT = 10 /* one launch = one whole SART sweep of the slab (volume-resident form) */,
+                      TOMO_K_PDHG_TV = 11 /* the fused pass of a Chambolle-Pock iteration */ };
 int tomo_profile_enable(tomo_engine *e, int kernel, int on);
 int tomo_profile_read(tomo_engine *e, int kernel, int64_t *launches, double *total_ms);
 /* the same, also busy_ms = time during which at least one launch of the kernel was executing (union of the launch

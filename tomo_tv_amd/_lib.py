@@ -16,7 +16,7 @@ SINO_YK_MODEL = 1000     # read-only: A * yk as tomo_fista_project_yk formed it
 VOL_USER0 = 5
 S_DD, S_DIFF, S_TV, S_GNORM, S_RMSE, S_COST, S_L1, S_DIFF2, S_GNORM_ALL, S_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 16
 FIELD_FGP_D, FIELD_FGP_P1 = 100, 101
-K_BP_ANGLE, K_FP_ANGLE, K_TV_GRAD, K_TV_UPDATE, K_FGP_OBJ, K_FGP_GRAD, K_SART_FUSED, K_FP_TILE, K_BP_TILE, K_FP_REDUCE, K_SART_RESIDENT = range(11)
+K_BP_ANGLE, K_FP_ANGLE, K_TV_GRAD, K_TV_UPDATE, K_FGP_OBJ, K_FGP_GRAD, K_SART_FUSED, K_FP_TILE, K_BP_TILE, K_FP_REDUCE, K_SART_RESIDENT, K_PDHG_TV = range(12)
 # tomo_form (tomo_get_option "form_fp" / "form_bp" / "form_sart"): the kernel family an operation of an engine runs as
 FORM_FP = ("rows", "tile", "strip", "list")
 FORM_BP = ("all", "tile", "list")
@@ -120,6 +120,10 @@ SIGNATURES = {
     "tomo_fgp_fused_step2": [_p, _f, _i],
     "tomo_fgp_fused_last": [_p, _f, _i],
     "tomo_fgp_fused_end": [_p, _f],
+    "tomo_pdhg_sino_dual": [_p, _i, _i, _i, _f, _i],
+    "tomo_pdhg_tv_step": [_p, _i, _i, _i, _i, _f, _f, _f, _f, _i, _i],
+    "tomo_pdhg_begin": [_p],
+    "tomo_pdhg": [_p, _i, _f, _f, _i, _f, _i],
     "tomo_get_stream": [_p, _pp],
     "tomo_mm_model": [_p, _p, _i, _p, _f, _p, _i],
     "tomo_mm_update": [_p, _p, _p, _i, _p, _f, _f, _f, _p, _i, _i],

@@ -78,6 +78,8 @@ static void free_geometry(tomo_engine *e)
     for (int i = 0; i < TOMO_SINO_SLOTS; ++i) if (e->sino[i]) { (void)hipFree(e->sino[i]); e->sino[i] = nullptr; }
     if (e->g_prev) { (void)hipFree(e->g_prev); e->g_prev = nullptr; }
     if (e->g_yk) { (void)hipFree(e->g_yk); e->g_yk = nullptr; }
+    if (e->pdhg_q) { (void)hipFree(e->pdhg_q); e->pdhg_q = nullptr; }
+    e->pdhg_begun = false;
     e->yk_claim.valid = false;
     e->g_prev_valid = e->mom_p_ok = e->mom.set = false;
     e->geometry_released = true;
@@ -100,7 +102,8 @@ int tomo_destroy(tomo_engine *e)
     if (e->rs_done) (void)hipHostFree(e->rs_done);
     free_geometry(e);
     void *ptrs[] = {e->tv_alt, e->halo_lo_alt, e->halo_hi_alt, e->d_part_tv, e->d_part_aux, e->fgp_q[0], e->fgp_q[1], e->fgp_q[2], e->cg_p, e->cg_z, e->cg_sums, e->cg_part, e->cg_coef, e->sart_alt,
-                    e->tvg, e->fgp_p[0], e->fgp_p[1], e->fgp_p[2], e->stage, e->d_scal_own, e->d_part, e->halo_lo_own, e->halo_hi_own};
+                    e->tvg, e->fgp_p[0], e->fgp_p[1], e->fgp_p[2], e->pdhg_p[0], e->pdhg_p[1], e->pdhg_p[2],
+                    e->pdhg_alt[0], e->pdhg_alt[1], e->pdhg_alt[2], e->pdhg_alt[3], e->stage, e->d_scal_own, e->d_part, e->halo_lo_own, e->halo_hi_own};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (int i = 0; i < TOMO_VOL_SLOTS; ++i) if (e->vol[i]) (void)hipFree(e->vol[i]);
     for (auto &p : e->prof) { for (auto ev : p.ev) (void)hipEventDestroy(ev); if (p.ref) (void)hipEventDestroy(p.ref); }

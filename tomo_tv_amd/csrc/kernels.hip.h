@@ -17,3 +17,4 @@
 #include "kernels_misc.hip.h"     // element-wise passes, reductions, multimodal, CGLS scalars, WBP filter
 #include "kernels_tv.hip.h"       // TV value / gradient / update
 #include "kernels_fgp.hip.h"      // FGP-TV
+#include "kernels_pdhg.hip.h"     // Chambolle-Pock: dual sinogram, fused dual / divergence / primal pass

@@ -278,6 +278,10 @@ struct tomo_engine {
     float *fgp_q[3] = {nullptr, nullptr, nullptr};   // ping-pong partners for the fused FGP iteration
     int fgp_fused = 1;
     int fgp_pair = 1;                             // ... two iterations per pass (k_fgp_fused2) where the slab is not sharded
+    // Chambolle-Pock (engine_pdhg.inc): the dual field and dual sinogram of the whole-call form, and the second buffers of the
+    // fused pass (xbar, p0..p2), which change places with the buffers of the fields it wrote
+    float *pdhg_p[3] = {nullptr, nullptr, nullptr}, *pdhg_alt[4] = {nullptr, nullptr, nullptr, nullptr}, *pdhg_q = nullptr;
+    bool pdhg_begun = false;
     float *stage = nullptr;
     size_t stage_bytes = 0;
     // scalars
@@ -503,6 +507,7 @@ extern "C" {
 
 #include "engine_api.inc"
 #include "engine_tv.inc"
+#include "engine_pdhg.inc"
 #include "engine_comm.inc"
 #include "engine_options.inc"
 

@@ -858,6 +858,35 @@ class _EngineBase:
         self.be.c("fista_project_yk", ctypes.byref(done))
         return bool(done.value)
 
+    # ---- Chambolle-Pock (include/tomo_hip.h: tomo_pdhg*) -----------------------------------------------------------------------
+    def _pdhg_one_engine(self):
+        """The iteration couples neighbouring slices through p and xbar; the slab-sharded form (halo planes of both) does not exist."""
+        if self.comm is not None or self.sub_slabs > 1 or not isinstance(self.be, _SlabBackend):
+            raise NotImplementedError("pdhg_tv runs on one whole-volume engine")
+
+    def pdhg_begin(self):
+        """p = 0, q = 0, xbar = recon: the state ``pdhg`` iterates on, kept until the next begin."""
+        self._pdhg_one_engine()
+        self.be.c("pdhg_begin")
+
+    def pdhg(self, niter, lam, theta=1.0, precond=True, ratio=1.0, slot=-1):
+        """``niter`` Chambolle-Pock iterations of min_{x >= 0} 1/2 |Ax - b|^2 + lam |grad x|_{2,1} on recon (after ``pdhg_begin``).
+        ``precond``: diagonal step sizes (no Lipschitz estimate, no tuning); False: scalar tau = ratio / sqrt(L_A + 12),
+        sigma = 1 / (ratio sqrt(L_A + 12)).  ``slot``: scalar slot that receives sum (x_new - x)^2 of the last iteration."""
+        self._pdhg_one_engine()
+        self.be.c("pdhg", int(niter), float(lam), float(theta), int(bool(precond)), float(ratio), int(slot))
+
+    def pdhg_sino_dual(self, q_sino, g_sino, b_sino, sigma=0.0, precond=True):
+        """Step form: q <- (q + S (g - b)) / (1 + S) on sinogram slots."""
+        self._pdhg_one_engine()
+        self.be.c("pdhg_sino_dual", int(q_sino), int(g_sino), int(b_sino), float(sigma), int(bool(precond)))
+
+    def pdhg_tv_step(self, x_vol, xbar_vol, u_vol, p_vol0, sigma=0.0, tau=0.0, lam=0.1, theta=1.0, precond=True, slot=-1):
+        """Step form: the fused dual / divergence / primal / extrapolation pass on volume slots (p in p_vol0 .. p_vol0 + 2)."""
+        self._pdhg_one_engine()
+        self.be.c("pdhg_tv_step", int(x_vol), int(xbar_vol), int(u_vol), int(p_vol0), float(sigma), float(tau), float(lam), float(theta),
+                  int(bool(precond)), int(slot))
+
     def synchronize(self):
         self.be.c("synchronize")
 

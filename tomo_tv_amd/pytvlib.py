@@ -16,6 +16,8 @@ def initialize_algorithm(tomo, alg, initAlg=""):
         tomo.initialize_CGLS()
     elif a == "fista":
         tomo.initialize_fista()
+    elif a == "pdhg":
+        pass                                   # Chambolle-Pock keeps its state in the engine (pdhg_begin); nothing to prepare
     elif a in ("poisson_ml", "kl-divergence"):
         tomo.initialize_poisson_ML()
     elif a in ("sart", "asd-pocs"):
@@ -25,9 +27,12 @@ def initialize_algorithm(tomo, alg, initAlg=""):
     tomo.initialize_FP()
 
 
-def run(tomo, alg, beta=1, niter=1):
-    """tomofusion/pytvlib.py:21-31 (plus the 'asd-pocs' -> SART branch the reference lacks, quirk Q8)."""
+def run(tomo, alg, beta=1, niter=1, **kw):
+    """tomofusion/pytvlib.py:21-31 (plus the 'asd-pocs' -> SART branch the reference lacks, quirk Q8, and 'pdhg': ``niter``
+    Chambolle-Pock iterations with lambda = ``beta``; ``theta``, ``precond``, ``ratio`` by keyword)."""
     a = alg.lower()
+    if a == "pdhg":
+        return tomo.pdhg(niter, beta, **kw)
     if a in ("sirt", "fista"):
         tomo.SIRT(niter)
     elif a == "cgls":

@@ -1,6 +1,6 @@
 """``TomoGPU`` -- the public reconstruction API of tomofusion/gpu/reconstructor.py:11-215 on the HIP engine.
 
-Same constructor and driver methods (``sirt``, ``sart``, ``fista``, ``asd_pocs``, ``kl_divergence``, ``get_recon``);
+Same constructor and driver methods (``sirt``, ``sart``, ``fista``, ``asd_pocs``, ``kl_divergence``, ``get_recon``), plus ``pdhg_tv``;
 the matplotlib/Tk viewers of the reference are not part of the hot path.  Broken reference drivers are implemented
 to the semantics of their canonical loops:
 ``fista`` is the textbook x_k = prox_TV(SIRT(y_k)) + momentum, ``asd_pocs`` follows examples/sim_ASD.py:66-94.
@@ -157,6 +157,31 @@ class TomoGPU:
                 self.cost[k] = 0.5 * t.data_distance() ** 2 + lambda_param * t.tv()
                 if momentum:
                     t.fista_project_yk()                      # the cost's A r gives the next step's A yk by linearity
+        return self.cost
+
+    def pdhg_tv(self, Niter=100, lambda_param=0.1, theta=1.0, precond=True, ratio=1.0, show_convergence=True):
+        """Chambolle-Pock (primal-dual hybrid gradient) for min_{x >= 0} 1/2 |Ax - b|^2 + lambda |grad x|_{2,1}: no inner loop, one
+        forward projection, one back projection and one fused stencil pass per iteration.  ``precond=True`` (default) uses the
+        diagonal step sizes of Pock and Chambolle (2011), which need no Lipschitz estimate; ``precond=False`` the scalar ones,
+        tau sigma (L_A + 12) = 1, with ``ratio`` moving weight from sigma to tau.  One whole-volume engine only.
+
+        With ``show_convergence`` the cost is ``0.5 * data_distance()**2 + lambda_param * tv()`` exactly as ``fista`` reports it.
+        ``tv()`` is the periodic, eps-smoothed value while the iteration minimises the Neumann one (no wrap-around, no eps);
+        FISTA with the FGP prox has the same mismatch."""
+        t = self.tomo
+        if not hasattr(t, "_pdhg_one_engine"):
+            raise NotImplementedError("pdhg_tv runs on one whole-volume engine")
+        t._pdhg_one_engine()
+        pytvlib.initialize_algorithm(t, "pdhg")
+        t.restart_recon()
+        t.pdhg_begin()
+        self.cost = np.zeros(Niter)
+        if not show_convergence:
+            pytvlib.run(t, "pdhg", lambda_param, Niter, theta=theta, precond=precond, ratio=ratio)
+            return self.cost
+        for k in range(Niter):
+            pytvlib.run(t, "pdhg", lambda_param, 1, theta=theta, precond=precond, ratio=ratio)
+            self.cost[k] = 0.5 * t.data_distance() ** 2 + lambda_param * t.tv()
         return self.cost
 
     @_on_rank_threads
