@@ -846,6 +846,45 @@ def test_rebuilding_the_stream_owner_of_a_multimodal_pair(gpu):
     assert mm.he.get_projections().shape == (Nx, 7 * N)
 
 
+def test_rebuild_and_teardown_with_every_ping_pong_pair_swapped(gpu):
+    """The engine's device buffers are owned by address, not by the member that holds them: tv_gd leaves the volume in tv_alt's
+    allocation, tv_fgp swaps fgp_p / fgp_q and hands fgp_q[0] to the volume (fused pair + fused last pass), pdhg rotates
+    pdhg_alt[] through xbar and the dual field.  A geometry rebuild in that state (volumes adopted, old engine destroyed), the same
+    calls again and the teardown must compute, bit for bit, what an engine without the rebuild computes, and the last destroy must
+    return without error: a buffer freed while still in use shows here as a differing volume.  (That each buffer is freed exactly
+    once is what tests/native/dev_pool_check.cpp asserts on the host.)"""
+    from tomo_tv_amd._lib import check
+    N, Nx, P = 16, 3, 5
+    ang = np.deg2rad(np.linspace(-60, 60, P))
+    x = ellipsoids(Nx, N, seed=6)
+    x0 = (0.5 * x + 0.1).astype(np.float32)
+
+    def calls(dev, b):
+        dev.set_tilt_series(b)
+        dev.tv_gd(3, 0.05)
+        dev.tv_fgp(4, 0.02)
+        dev.pdhg_begin()
+        dev.pdhg(2, 0.05)
+        dev.SART(0.5, 1)
+
+    out = []
+    for rebuild in (True, False):
+        dev = tomoengine(Nx, N, ang)
+        dev.set_volume(x, VOL_ORIGINAL)
+        dev.create_projections()
+        b = dev.get_projections()
+        dev.set_volume(x0, VOL_RECON)
+        calls(dev, b)
+        if rebuild:
+            dev.update_projection_angles(ang)
+        calls(dev, b)
+        out.append(dev.get_volume())
+        h, dev.be.h = dev.be.h, None
+        check(dev.be.L.tomo_destroy(h))
+    assert np.isfinite(out[0]).all() and np.abs(out[0]).max() > 0
+    assert np.array_equal(out[0], out[1])
+
+
 @pytest.mark.parametrize("N,P,Nx", [(40, 7, 70), (96, 13, 128), (33, 5, 256)])
 def test_tile_projectors_match_row_and_pixel_driven_forms(gpu, N, P, Nx):
     """k_fp_tile/k_fp_tile_reduce and k_bp_tile against the ray-driven FP and the pixel-driven BP they replace:

@@ -61,24 +61,8 @@ int tomo_create_from_matrix(int nslice, int nray, int nproj, int64_t nnz, const 
 // every device buffer that depends on the tilt geometry (tables, sinograms, scratch sized by it); volumes stay
 static void free_geometry(tomo_engine *e)
 {
-    void **ptrs[] = {(void **)&e->d_st_cell, (void **)&e->d_st_win, (void **)&e->d_st_segid, (void **)&e->d_st_seg, (void **)&e->d_st_ent,
-                     (void **)&e->d_st_row_first, (void **)&e->d_st_row_nseg, (void **)&e->st_partial, (void **)&e->st_partial2, (void **)&e->st_flags, (void **)&e->d_fb_cell, (void **)&e->d_fb_win, (void **)&e->d_bl_ent, (void **)&e->d_bl_ptr, (void **)&e->d_bl_win,
-                     (void **)&e->d_ft_slot_ptr, (void **)&e->d_ft_slot_seg0, (void **)&e->d_ft_tent, (void **)&e->d_ft_rsptr, (void **)&e->d_ft_rsidx,
-                     (void **)&e->ft_part, (void **)&e->ft_part_aux, (void **)&e->cg_w, (void **)&e->fbp_h, (void **)&e->d_seg_exec,
-                     (void **)&e->d_row_first, (void **)&e->d_row_nseg, (void **)&e->seg_partial, (void **)&e->d_wptr, (void **)&e->d_went,
-                     (void **)&e->d_rptr, (void **)&e->d_rent, (void **)&e->d_rowsum, (void **)&e->d_rowinner, (void **)&e->d_colsum_all,
-                     (void **)&e->d_rowcross, (void **)&e->d_cell,
-                     (void **)&e->d_fs_items, (void **)&e->d_fs_orient, (void **)&e->d_fs_shift, (void **)&e->d_fs_cnt, (void **)&e->d_fs_gstart,
-                     (void **)&e->d_fs_gseg0, (void **)&e->d_fs_ent, (void **)&e->d_fs_zero, (void **)&e->d_fs_rsptr, (void **)&e->d_fs_rsidx, (void **)&e->fs_part, (void **)&e->fs_part_aux,
-                     (void **)&e->d_fl_items, (void **)&e->d_fl_orient, (void **)&e->d_fl_shift, (void **)&e->d_fl_ent, (void **)&e->d_fl_ptr, (void **)&e->d_fl_fent, (void **)&e->d_fl_fptr,
-                     (void **)&e->d_fl_rsptr, (void **)&e->d_fl_rsidx, (void **)&e->d_fl_zero, (void **)&e->fl_part, (void **)&e->fl_part_aux,
-                     (void **)&e->d_rs_hdr, (void **)&e->d_rs_cell, (void **)&e->d_rs_ts, (void **)&e->d_rs_rl, (void **)&e->rs_pb, (void **)&e->rs_rb, (void **)&e->d_rs_angs, (void **)&e->d_rs_abort, (void **)&e->d_rs_commit};
-    for (void **p : ptrs) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    e->pool.release_life(GEOMETRY);
     e->rs_ok = false; e->rs_angs_cap = 0; e->rs_angs_host.clear(); e->seg_ready = false;
-    for (int i = 0; i < TOMO_SINO_SLOTS; ++i) if (e->sino[i]) { (void)hipFree(e->sino[i]); e->sino[i] = nullptr; }
-    if (e->g_prev) { (void)hipFree(e->g_prev); e->g_prev = nullptr; }
-    if (e->g_yk) { (void)hipFree(e->g_yk); e->g_yk = nullptr; }
-    if (e->pdhg_q) { (void)hipFree(e->pdhg_q); e->pdhg_q = nullptr; }
     e->pdhg_begun = false;
     e->yk_claim.valid = false;
     e->g_prev_valid = e->mom_p_ok = e->mom.set = false;
@@ -100,12 +84,7 @@ int tomo_destroy(tomo_engine *e)
     if (e->h_snap) (void)hipHostFree(e->h_snap);
     if (e->rs_abort) (void)hipHostFree(e->rs_abort);
     if (e->rs_done) (void)hipHostFree(e->rs_done);
-    free_geometry(e);
-    void *ptrs[] = {e->tv_alt, e->halo_lo_alt, e->halo_hi_alt, e->d_part_tv, e->d_part_aux, e->fgp_q[0], e->fgp_q[1], e->fgp_q[2], e->cg_p, e->cg_z, e->cg_sums, e->cg_part, e->cg_coef, e->sart_alt,
-                    e->tvg, e->fgp_p[0], e->fgp_p[1], e->fgp_p[2], e->pdhg_p[0], e->pdhg_p[1], e->pdhg_p[2],
-                    e->pdhg_alt[0], e->pdhg_alt[1], e->pdhg_alt[2], e->pdhg_alt[3], e->stage, e->d_scal_own, e->d_part, e->halo_lo_own, e->halo_hi_own};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    for (int i = 0; i < TOMO_VOL_SLOTS; ++i) if (e->vol[i]) (void)hipFree(e->vol[i]);
+    e->pool.release_all();
     for (auto &p : e->prof) { for (auto ev : p.ev) (void)hipEventDestroy(ev); if (p.ref) (void)hipEventDestroy(p.ref); }
     if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
@@ -136,11 +115,11 @@ int tomo_adopt_volumes(tomo_engine *dst, tomo_engine *src)
     for (int u = 0; u < tomo_engine::MAX_CHAINS; ++u) if (src->sub_stream[u]) HIPCHK(hipStreamSynchronize(src->sub_stream[u]));
     src->async_pending = false;
     HIPCHK(hipStreamSynchronize(dst->stream));
-    for (int i = 0; i < TOMO_VOL_SLOTS; ++i) {
+    for (int i = 0; i < TOMO_VOL_SLOTS; ++i) {      // (an error return in here leaves the volumes before i moved: it cannot fire for engines whose volumes are their own)
         if (!src->vol[i]) continue;
-        if (dst->vol[i]) HIPCHK(hipFree(dst->vol[i]));
-        dst->vol[i] = src->vol[i];
-        src->vol[i] = nullptr;
+        if (dst->vol[i] && dst->pool.release(dst->vol[i])) return fail(TOMO_ERR_STATE, "a volume of the adopting engine is not its own");
+        if (src->pool.move_to(dst->pool, src->vol[i], (void **)&dst->vol[i])) return fail(TOMO_ERR_STATE, "a volume of the adopted engine is not its own");
+        src->vol[i] = nullptr;                     // (its entry's slot may be the partner of a swap: move_to nulls only a slot that held the address)
     }
     dst->old_is_recon = src->old_is_recon;
     src->old_is_recon = false;
@@ -395,8 +374,8 @@ static int launch_sart_resident(tomo_engine *e, float *x, float beta, int64_t st
         if (seq != e->rs_angs_host) {
             HIPCHK(hipStreamSynchronize(e->stream));          // (a sweep in flight may still read the old sequence; rare: the first sweep, a new order)
             if ((size_t)steps > e->rs_angs_cap) {
-                if (e->d_rs_angs) { HIPCHK(hipFree(e->d_rs_angs)); e->d_rs_angs = nullptr; e->rs_angs_cap = 0; }
-                HIPCHK(hipMalloc((void **)&e->d_rs_angs, (size_t)steps * sizeof(int)));
+                if (e->d_rs_angs) { e->pool.release(e->d_rs_angs); e->rs_angs_cap = 0; }
+                if (int rc = dev_alloc(e, GEOMETRY, (void **)&e->d_rs_angs, (size_t)steps * sizeof(int), false)) return rc;
                 e->rs_angs_cap = (size_t)steps;
             }
             HIPCHK(hipMemcpy(e->d_rs_angs, seq.data(), (size_t)steps * sizeof(int), hipMemcpyHostToDevice));
@@ -704,7 +683,7 @@ static int slice_sumsq(tomo_engine *e, const float *v, int64_t m, double *sums)
     const int cols = e->sx / 4, per = cols >= 256 ? 256 : (cols >= 128 ? 128 : 64);
     const int nby = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (m + 63) / 64));   // workgroups along the rows
     const int rpb = (int)((m + nby - 1) / nby);
-    if (!e->cg_part) { int rc = dev_alloc((void **)&e->cg_part, (size_t)1024 * e->sx * sizeof(double), false, e->stream); if (rc) return rc; }
+    if (!e->cg_part) { int rc = dev_alloc(e, ENGINE, (void **)&e->cg_part, (size_t)1024 * e->sx * sizeof(double), false); if (rc) return rc; }
     dim3 grid((unsigned)((cols + per - 1) / per), (unsigned)nby);
     hipLaunchKernelGGL(k_slice_sumsq, grid, dim3(256), 0, e->stream, v, e->cg_part, m, e->sx, rpb);
     LAUNCHCHK();
@@ -732,8 +711,8 @@ int tomo_cgls(tomo_engine *e, int vol, int niter)
     if ((rc = get_vol(e, vol, &x)) || (rc = get_sino(e, &e->sino[TOMO_SINO_R], &r)) || (rc = sino_slot(e, TOMO_SINO_B, &b))) return rc;
     if ((rc = get_scratch(e, &e->cg_p, &w)) || (rc = get_scratch(e, &e->cg_z, &w))) return rc;
     if ((rc = get_sino(e, &e->cg_w, &w))) return rc;
-    if (!e->cg_sums) { if ((rc = dev_alloc((void **)&e->cg_sums, 2 * e->sx * sizeof(double), true, e->stream))) return rc; }
-    if (!e->cg_coef) { if ((rc = dev_alloc((void **)&e->cg_coef, e->sx * sizeof(float), true, e->stream))) return rc; }
+    if (!e->cg_sums) { if ((rc = dev_alloc(e, ENGINE, (void **)&e->cg_sums, 2 * e->sx * sizeof(double), true))) return rc; }
+    if (!e->cg_coef) { if ((rc = dev_alloc(e, ENGINE, (void **)&e->cg_coef, e->sx * sizeof(float), true))) return rc; }
     double *gam = e->cg_sums, *tmp = e->cg_sums + e->sx;
     const int64_t nv = (int64_t)e->vol_elems(), ns = (int64_t)e->sino_elems();
     auto ratio = [&](const double *num, const double *den) {
@@ -771,7 +750,7 @@ int tomo_fbp(tomo_engine *e, const float *taps_host, float scale, int apply_posi
     if (!taps_host) return fail(TOMO_ERR_ARG, "null filter");
     float *x, *b, *g; int rc;
     if ((rc = get_vol(e, TOMO_VOL_RECON, &x)) || (rc = sino_slot(e, TOMO_SINO_B, &b)) || (rc = get_sino(e, &e->sino[TOMO_SINO_R], &g))) return rc;
-    if (!e->fbp_h) { if ((rc = dev_alloc((void **)&e->fbp_h, e->n * sizeof(float), false, e->stream))) return rc; }
+    if (!e->fbp_h) { if ((rc = dev_alloc(e, GEOMETRY, (void **)&e->fbp_h, e->n * sizeof(float), false))) return rc; }
     HIPCHK(hipMemcpyAsync(e->fbp_h, taps_host, e->n * sizeof(float), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     int nchunk = e->sxc / (64 * e->vec);
@@ -1012,8 +991,7 @@ int tomo_data_distance_sq_async(tomo_engine *e, int vol)
         HIPCHK(hipStreamCreateWithFlags(&e->aux, hipStreamNonBlocking));
         HIPCHK(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
-        int rc = dev_alloc((void **)&e->d_part_aux, NPART * sizeof(double), true, e->stream);
-        if (rc) return rc;
+        if (int rc = dev_alloc(e, ENGINE, (void **)&e->d_part_aux, NPART * sizeof(double), true)) return rc;
     }
     float *tmp; int rc;
     if ((rc = get_vol_ro(e, vol, &tmp)) || (rc = get_sino(e, &e->sino[TOMO_SINO_G], &tmp))) return rc;   // allocate on the main stream

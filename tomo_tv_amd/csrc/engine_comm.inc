@@ -66,11 +66,7 @@ static void comm_release(tomo_engine *e)
     }
     e->comm = nullptr;
     if (e->comm_fgp && e->fgp_lo == e->comm_fgp) { e->fgp_lo = e->fgp_hi = e->fgp_send_first = e->fgp_send_last = nullptr; e->fgp_planes2 = false; }
-    void *ptrs[] = {e->comm_send_first, e->comm_send_last, e->comm_g_lo, e->comm_g_hi, e->comm_scal, e->comm_fgp};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    e->comm_fgp = nullptr;
-    e->comm_send_first = e->comm_send_last = e->comm_g_lo = e->comm_g_hi = nullptr;
-    e->comm_scal = nullptr;
+    e->pool.release_life(COMM);
 }
 
 static int comm_buffers(tomo_engine *e)
@@ -78,13 +74,13 @@ static int comm_buffers(tomo_engine *e)
     if (e->comm_scal) return TOMO_OK;
     int rc;
     float **planes[] = {&e->comm_send_first, &e->comm_send_last, &e->comm_g_lo, &e->comm_g_hi};
-    for (float **p : planes) if ((rc = dev_alloc((void **)p, e->npix * sizeof(float), true, e->stream))) return rc;
+    for (float **p : planes) if ((rc = dev_alloc(e, COMM, (void **)p, e->npix * sizeof(float), true))) return rc;
     if (!e->fgp_lo) {        // a host that binds no planes of its own (tomo_bind_fgp_halo / _halo2) gets the engine's, the deep set: lo 5, hi 8, send_first 8, send_last 5
-        if ((rc = dev_alloc((void **)&e->comm_fgp, 26 * e->npix * sizeof(float), true, e->stream))) return rc;
+        if ((rc = dev_alloc(e, COMM, (void **)&e->comm_fgp, 26 * e->npix * sizeof(float), true))) return rc;
         e->fgp_lo = e->comm_fgp; e->fgp_hi = e->comm_fgp + 5 * e->npix; e->fgp_send_first = e->comm_fgp + 13 * e->npix; e->fgp_send_last = e->comm_fgp + 21 * e->npix;
         e->fgp_planes2 = true;
     }
-    return dev_alloc((void **)&e->comm_scal, TOMO_S_COUNT * sizeof(double), true, e->stream);
+    return dev_alloc(e, COMM, (void **)&e->comm_scal, TOMO_S_COUNT * sizeof(double), true);
 }
 
 // ring exchange inside an open group: my last plane(s) -> next's lo, my first plane(s) -> prev's hi.  With prev == next (two

@@ -6,6 +6,31 @@
 // and one process per GPU builds its own)
 template <class V> static void release(V &v) { V().swap(v); }
 
+// Host tables onto the device.  A Tab names one: the member that will hold it, the host data, and the least size of its allocation (what the
+// kernels may address of a table that can be empty, or prefetch behind its end); tab() makes one of a vector, or of a pointer and its bytes.
+struct Tab { void **slot; const void *host; size_t bytes, min_bytes; };
+template <class D, class T> static Tab tab(D **slot, const std::vector<T> &v, size_t min_elems = 0) { return Tab{(void **)slot, v.data(), v.size() * sizeof(T), min_elems * sizeof(T)}; }
+template <class D> static Tab tab(D **slot, const void *host, size_t bytes) { return Tab{(void **)slot, host, bytes, 0}; }
+// each table allocated (the geometry's memory) and then copied, in the order given; the first error ends it
+static int upload_tables(tomo_engine *e, std::initializer_list<Tab> tabs)
+{
+    for (const Tab &t : tabs) {
+        int rc = dev_alloc(e, GEOMETRY, t.slot, std::max(t.bytes, t.min_bytes), false);
+        if (rc) return rc;
+        HIPCHK(hipMemcpy(*t.slot, t.host, t.bytes, hipMemcpyHostToDevice));
+    }
+    return TOMO_OK;
+}
+
+// matrix entries as the kernels load them: {offset, the weight's bits}
+template <class O>
+static std::vector<uint2> pack_entries(const O *off, const float *w, size_t n)
+{
+    std::vector<uint2> ent(n);
+    for (size_t k = 0; k < n; ++k) { uint32_t bits; std::memcpy(&bits, &w[k], 4); ent[k] = make_uint2((uint32_t)off[k], bits); }
+    return ent;
+}
+
 // Walk lists + equal-sized segment items of the ray-walk SART step (k_sart_seg): the form of matrices whose tile tables do not exist and
 // of "sart_tile" = 0.  Round 6: where the tile tables exist and the engine knows its angles, these tables are built on first use
 // (ensure_seg_tables) instead of at creation -- 0.19 of 2.3 s at 512^2 x 90, 0.93 of 9.4 s at 1024^2 x 120, 0.25 / 1.4 GB of device
@@ -16,12 +41,8 @@ static int build_seg_tables(tomo_engine *e, const Coo &m, Tables &t)
     int rc;
     build_walk(m, e->n, e->np, t);
     {
-        std::vector<uint2> went(t.walk_pix.size() ? t.walk_pix.size() : 1);
-        for (size_t k = 0; k < t.walk_pix.size(); ++k) { uint32_t bits; std::memcpy(&bits, &t.walk_w[k], 4); went[k] = make_uint2(t.walk_pix[k], bits); }
-        if ((rc = dev_alloc((void **)&e->d_wptr, t.walk_ptr.size() * 4, false, e->stream))) return rc;
-        if ((rc = dev_alloc((void **)&e->d_went, went.size() * sizeof(uint2), false, e->stream))) return rc;
-        HIPCHK(hipMemcpy(e->d_wptr, t.walk_ptr.data(), t.walk_ptr.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(e->d_went, went.data(), t.walk_pix.size() * sizeof(uint2), hipMemcpyHostToDevice));
+        const std::vector<uint2> went = pack_entries(t.walk_pix.data(), t.walk_w.data(), t.walk_pix.size());
+        if ((rc = upload_tables(e, {tab(&e->d_wptr, t.walk_ptr), tab(&e->d_went, went, 1)}))) return rc;
     }
     {
         const int seg_len = 32;   // visits per work item: 16/32/64/128 measured 222/224/233/242 us per fused step at 512^3
@@ -29,12 +50,7 @@ static int build_seg_tables(tomo_engine *e, const Coo &m, Tables &t)
         static_assert(sizeof(Tables::SegItem) == sizeof(SegItemD), "segment item layout");
         e->h_seg_exec_ptr = t.seg_exec_ptr;
         e->max_items = t.max_items_per_angle;
-        if ((rc = dev_alloc((void **)&e->d_seg_exec, std::max<size_t>(1, t.seg_exec.size()) * sizeof(SegItemD), false, e->stream))) return rc;
-        if ((rc = dev_alloc((void **)&e->d_row_first, t.row_first.size() * 4, false, e->stream))) return rc;
-        if ((rc = dev_alloc((void **)&e->d_row_nseg, t.row_nseg.size() * 4, false, e->stream))) return rc;
-        HIPCHK(hipMemcpy(e->d_seg_exec, t.seg_exec.data(), t.seg_exec.size() * sizeof(SegItemD), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(e->d_row_first, t.row_first.data(), t.row_first.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(e->d_row_nseg, t.row_nseg.data(), t.row_nseg.size() * 4, hipMemcpyHostToDevice));
+        if ((rc = upload_tables(e, {tab(&e->d_seg_exec, t.seg_exec, 1), tab(&e->d_row_first, t.row_first), tab(&e->d_row_nseg, t.row_nseg)}))) return rc;
         release(t.walk_pix); release(t.walk_w); release(t.walk_ptr); release(t.seg_exec); release(t.row_first); release(t.row_nseg);
     }
     e->seg_ready = true;
@@ -62,7 +78,6 @@ static int finish_create_impl(tomo_engine *e, Coo &m, tomo_engine **out)
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t_last = now();
     auto lap = [&](const char *what) { if (timing) { double x = now(); std::fprintf(stderr, "tomo_create: %-32s %.3f s\n", what, x - t_last); t_last = x; } };
-    struct Meter { Meter(size_t *p) { g_alloc_meter = p; } ~Meter() { g_alloc_meter = nullptr; } } meter(&e->table_bytes);
     sort_rows(m);
     lap("sort_rows");
     if (!build_tables(m, e->n, e->np, t, err)) return fail(TOMO_ERR_GEOMETRY, err);
@@ -77,41 +92,20 @@ static int finish_create_impl(tomo_engine *e, Coo &m, tomo_engine **out)
 
     std::vector<uint32_t> ptr32(m.nrow + 1);
     for (int64_t r = 0; r <= m.nrow; ++r) ptr32[r] = (uint32_t)m.ptr[r];
-    std::vector<uint2> ent(e->nnz ? e->nnz : 1);
-    for (int64_t k = 0; k < e->nnz; ++k) { uint32_t bits; std::memcpy(&bits, &m.val[k], 4); ent[k] = make_uint2(m.col[k], bits); }
+    std::vector<uint2> ent = pack_entries(m.col.data(), m.val.data(), (size_t)e->nnz);
     int rc;
-    if ((rc = dev_alloc((void **)&e->d_rptr, ptr32.size() * 4, false, e->stream))) return rc;
-    if ((rc = dev_alloc((void **)&e->d_rent, ent.size() * sizeof(uint2), false, e->stream))) return rc;
-    if ((rc = dev_alloc((void **)&e->d_rowsum, t.rowsum.size() * 4, false, e->stream))) return rc;
-    if ((rc = dev_alloc((void **)&e->d_rowinner, t.rowinner.size() * 4, false, e->stream))) return rc;
-    if ((rc = dev_alloc((void **)&e->d_colsum_all, t.colsum_all.size() * 4, false, e->stream))) return rc;
-    if ((rc = dev_alloc((void **)&e->d_rowcross, t.rowcross.size() * 4, false, e->stream))) return rc;
-    e->art_chain_ok = t.art_chain_ok;
-    if ((rc = dev_alloc((void **)&e->d_cell, t.cell.size() * sizeof(CellD), false, e->stream))) return rc;
-    HIPCHK(hipMemcpy(e->d_rptr, ptr32.data(), ptr32.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_rent, ent.data(), (size_t)e->nnz * sizeof(uint2), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_rowsum, t.rowsum.data(), t.rowsum.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_rowinner, t.rowinner.data(), t.rowinner.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_colsum_all, t.colsum_all.data(), t.colsum_all.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_rowcross, t.rowcross.data(), t.rowcross.size() * 4, hipMemcpyHostToDevice));
+    if ((rc = upload_tables(e, {tab(&e->d_rptr, ptr32), tab(&e->d_rent, ent, 1), tab(&e->d_rowsum, t.rowsum), tab(&e->d_rowinner, t.rowinner),
+                                tab(&e->d_colsum_all, t.colsum_all), tab(&e->d_rowcross, t.rowcross), tab(&e->d_cell, t.cell)}))) return rc;
+    e->art_chain_ok = t.art_chain_ok;      // (the cells go up here: build_tables wrote them, every later builder only reads them)
     lap("csr / cells upload");
     {
         build_tiles(m, e->n, e->np, FT_TY, FT_TZ, 256, t);
         static_assert(Tables::TILE_SLOTS == FT_SLOTS && Tables::TILE_BATCH == FT_BATCH, "tile stream shape");
         e->ft_tiles_z = t.tiles_z; e->ft_ntiles = t.tiles_y * t.tiles_z;
         e->ft_nseg = t.tile_nseg;
-        std::vector<uint2> tent(t.tile_off.size());
-        for (size_t k = 0; k < tent.size(); ++k) { uint32_t bits; std::memcpy(&bits, &t.tile_w[k], 4); tent[k] = make_uint2(t.tile_off[k], bits); }
-        if ((rc = dev_alloc((void **)&e->d_ft_slot_ptr, t.tile_slot_ptr.size() * 4, false, e->stream))) return rc;
-        if ((rc = dev_alloc((void **)&e->d_ft_slot_seg0, std::max<size_t>(1, t.tile_slot_seg0.size()) * 4, false, e->stream))) return rc;
-        if ((rc = dev_alloc((void **)&e->d_ft_tent, tent.size() * sizeof(uint2), false, e->stream))) return rc;
-        if ((rc = dev_alloc((void **)&e->d_ft_rsptr, t.rseg_ptr.size() * 4, false, e->stream))) return rc;
-        if ((rc = dev_alloc((void **)&e->d_ft_rsidx, t.rseg_idx.size() * 4, false, e->stream))) return rc;
-        HIPCHK(hipMemcpy(e->d_ft_slot_ptr, t.tile_slot_ptr.data(), t.tile_slot_ptr.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(e->d_ft_slot_seg0, t.tile_slot_seg0.data(), t.tile_slot_seg0.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(e->d_ft_tent, tent.data(), tent.size() * sizeof(uint2), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(e->d_ft_rsptr, t.rseg_ptr.data(), t.rseg_ptr.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(e->d_ft_rsidx, t.rseg_idx.data(), t.rseg_idx.size() * 4, hipMemcpyHostToDevice));
+        std::vector<uint2> tent = pack_entries(t.tile_off.data(), t.tile_w.data(), t.tile_off.size());
+        if ((rc = upload_tables(e, {tab(&e->d_ft_slot_ptr, t.tile_slot_ptr), tab(&e->d_ft_slot_seg0, t.tile_slot_seg0, 1), tab(&e->d_ft_tent, tent),
+                                    tab(&e->d_ft_rsptr, t.rseg_ptr), tab(&e->d_ft_rsidx, t.rseg_idx)}))) return rc;
         release(tent); release(t.tile_off); release(t.tile_w); release(t.rseg_idx); release(t.rseg_ptr); release(t.tile_slot_ptr); release(t.tile_slot_seg0);
         lap("build_tiles + upload");
         {   // sheared-strip tables of the all-angle FP; a geometry they cannot hold (a user matrix whose rays are no lines) keeps the tile form
@@ -131,25 +125,10 @@ static int finish_create_impl(tomo_engine *e, Coo &m, tomo_engine **out)
             if (e->fs_ok) {
                 e->fs_nitems = (int)t.fs_item.size(); e->fs_kused = t.fs_kused; e->fs_nseg = t.fs_nseg;
                 static_assert(sizeof(uint2) == sizeof(uint64_t), "entry layout");
-                if ((rc = dev_alloc((void **)&e->d_fs_items, t.fs_item.size() * sizeof(FsItemD), false, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->d_fs_orient, t.fs_orient.size() * 4, false, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->d_fs_shift, t.fs_shift.size() * 4, false, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->d_fs_cnt, t.fs_cnt.size(), false, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->d_fs_gstart, t.fs_gstart.size() * 4, false, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->d_fs_gseg0, t.fs_gseg0.size() * 4, false, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->d_fs_ent, t.fs_ent_n * sizeof(uint2), false, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->d_fs_rsptr, t.fs_rseg_ptr.size() * 4, false, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->d_fs_rsidx, t.fs_rseg_idx.size() * 4, false, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->d_fs_zero, 256, true, e->stream))) return rc;
-                HIPCHK(hipMemcpy(e->d_fs_items, t.fs_item.data(), t.fs_item.size() * sizeof(FsItemD), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(e->d_fs_orient, t.fs_orient.data(), t.fs_orient.size() * 4, hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(e->d_fs_shift, t.fs_shift.data(), t.fs_shift.size() * 4, hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(e->d_fs_cnt, t.fs_cnt.data(), t.fs_cnt.size(), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(e->d_fs_gstart, t.fs_gstart.data(), t.fs_gstart.size() * 4, hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(e->d_fs_gseg0, t.fs_gseg0.data(), t.fs_gseg0.size() * 4, hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(e->d_fs_ent, t.fs_ent.get(), t.fs_ent_n * sizeof(uint2), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(e->d_fs_rsptr, t.fs_rseg_ptr.data(), t.fs_rseg_ptr.size() * 4, hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(e->d_fs_rsidx, t.fs_rseg_idx.data(), t.fs_rseg_idx.size() * 4, hipMemcpyHostToDevice));
+                if ((rc = upload_tables(e, {tab(&e->d_fs_items, t.fs_item), tab(&e->d_fs_orient, t.fs_orient), tab(&e->d_fs_shift, t.fs_shift), tab(&e->d_fs_cnt, t.fs_cnt),
+                                            tab(&e->d_fs_gstart, t.fs_gstart), tab(&e->d_fs_gseg0, t.fs_gseg0), tab(&e->d_fs_ent, t.fs_ent.get(), t.fs_ent_n * sizeof(uint2)),
+                                            tab(&e->d_fs_rsptr, t.fs_rseg_ptr), tab(&e->d_fs_rsidx, t.fs_rseg_idx)}))) return rc;
+                if ((rc = dev_alloc(e, GEOMETRY, (void **)&e->d_fs_zero, 256, true))) return rc;
             }
             t.fs_ent.reset(); t.fs_ent_n = 0; release(t.fs_cnt); release(t.fs_rseg_idx); release(t.fs_rseg_ptr); release(t.fs_gstart); release(t.fs_gseg0);
         }
@@ -168,25 +147,10 @@ static int finish_create_impl(tomo_engine *e, Coo &m, tomo_engine **out)
             if (e->fl_ok && !std::getenv("TOMO_FP_LIST") && t.fl_balance < 0.8) e->fl_ok = false;
             if (e->fl_ok) {
                 e->fl_nitems = (int)t.fl_item.size(); e->fl_nseg = t.fl_nseg;
-                if ((rc = dev_alloc((void **)&e->d_fl_items, t.fl_item.size() * sizeof(FlItemD), false, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->d_fl_orient, t.fl_orient.size() * 4, false, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->d_fl_shift, t.fl_shift.size() * 4, false, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->d_fl_ent, t.fl_ent_n * sizeof(uint2), false, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->d_fl_ptr, t.fl_ptr.size() * 4, false, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->d_fl_fent, t.fl_flush.size() * sizeof(uint2), false, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->d_fl_fptr, t.fl_fptr.size() * 4, false, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->d_fl_rsptr, t.fl_rseg_ptr.size() * 4, false, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->d_fl_rsidx, t.fl_rseg_idx.size() * 4, false, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->d_fl_zero, 512, true, e->stream))) return rc;
-                HIPCHK(hipMemcpy(e->d_fl_items, t.fl_item.data(), t.fl_item.size() * sizeof(FlItemD), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(e->d_fl_orient, t.fl_orient.data(), t.fl_orient.size() * 4, hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(e->d_fl_shift, t.fl_shift.data(), t.fl_shift.size() * 4, hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(e->d_fl_ent, t.fl_ent.get(), t.fl_ent_n * sizeof(uint2), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(e->d_fl_ptr, t.fl_ptr.data(), t.fl_ptr.size() * 4, hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(e->d_fl_fent, t.fl_flush.data(), t.fl_flush.size() * sizeof(uint2), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(e->d_fl_fptr, t.fl_fptr.data(), t.fl_fptr.size() * 4, hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(e->d_fl_rsptr, t.fl_rseg_ptr.data(), t.fl_rseg_ptr.size() * 4, hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(e->d_fl_rsidx, t.fl_rseg_idx.data(), t.fl_rseg_idx.size() * 4, hipMemcpyHostToDevice));
+                if ((rc = upload_tables(e, {tab(&e->d_fl_items, t.fl_item), tab(&e->d_fl_orient, t.fl_orient), tab(&e->d_fl_shift, t.fl_shift),
+                                            tab(&e->d_fl_ent, t.fl_ent.get(), t.fl_ent_n * sizeof(uint2)), tab(&e->d_fl_ptr, t.fl_ptr), tab(&e->d_fl_fent, t.fl_flush),
+                                            tab(&e->d_fl_fptr, t.fl_fptr), tab(&e->d_fl_rsptr, t.fl_rseg_ptr), tab(&e->d_fl_rsidx, t.fl_rseg_idx)}))) return rc;
+                if ((rc = dev_alloc(e, GEOMETRY, (void **)&e->d_fl_zero, 512, true))) return rc;
             }
             t.fl_ent.reset(); t.fl_ent_n = 0; release(t.fl_flush); release(t.fl_ptr); release(t.fl_fptr); release(t.fl_rseg_ptr); release(t.fl_rseg_idx); release(t.fl_item); release(t.fl_shift);
         }
@@ -196,22 +160,9 @@ static int finish_create_impl(tomo_engine *e, Coo &m, tomo_engine **out)
         e->st_ok = t.st_ok;
         if (e->st_ok) {
             e->st_ntiles = t.st_tiles; e->st_tiles_z = t.st_tiles_z; e->st_max_ids = t.st_max_ids;
-            std::vector<uint2> sent(t.st_off.size());
-            for (size_t k = 0; k < sent.size(); ++k) { uint32_t bits; std::memcpy(&bits, &t.st_w[k], 4); sent[k] = make_uint2(t.st_off[k], bits); }
-            if ((rc = dev_alloc((void **)&e->d_st_cell, t.st_cell.size() * sizeof(uint4), false, e->stream))) return rc;
-            if ((rc = dev_alloc((void **)&e->d_st_win, t.st_win.size() * 4, false, e->stream))) return rc;
-            if ((rc = dev_alloc((void **)&e->d_st_segid, t.st_segid.size() * 4, false, e->stream))) return rc;
-            if ((rc = dev_alloc((void **)&e->d_st_seg, t.st_seg.size() * 4, false, e->stream))) return rc;
-            if ((rc = dev_alloc((void **)&e->d_st_ent, sent.size() * sizeof(uint2), false, e->stream))) return rc;
-            if ((rc = dev_alloc((void **)&e->d_st_row_first, t.st_row_first.size() * 4, false, e->stream))) return rc;
-            if ((rc = dev_alloc((void **)&e->d_st_row_nseg, t.st_row_nseg.size() * 4, false, e->stream))) return rc;
-            HIPCHK(hipMemcpy(e->d_st_cell, t.st_cell.data(), t.st_cell.size() * sizeof(uint4), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(e->d_st_win, t.st_win.data(), t.st_win.size() * 4, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(e->d_st_segid, t.st_segid.data(), t.st_segid.size() * 4, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(e->d_st_seg, t.st_seg.data(), t.st_seg.size() * 4, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(e->d_st_ent, sent.data(), sent.size() * sizeof(uint2), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(e->d_st_row_first, t.st_row_first.data(), t.st_row_first.size() * 4, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(e->d_st_row_nseg, t.st_row_nseg.data(), t.st_row_nseg.size() * 4, hipMemcpyHostToDevice));
+            const std::vector<uint2> sent = pack_entries(t.st_off.data(), t.st_w.data(), t.st_off.size());
+            if ((rc = upload_tables(e, {tab(&e->d_st_cell, t.st_cell), tab(&e->d_st_win, t.st_win), tab(&e->d_st_segid, t.st_segid), tab(&e->d_st_seg, t.st_seg),
+                                        tab(&e->d_st_ent, sent), tab(&e->d_st_row_first, t.st_row_first), tab(&e->d_st_row_nseg, t.st_row_nseg)}))) return rc;
         }
         release(t.st_cell); release(t.st_off); release(t.st_w); release(t.st_seg); release(t.st_segid); release(t.st_win);
         lap("build_sart_tiles + upload");
@@ -240,19 +191,10 @@ static int finish_create_impl(tomo_engine *e, Coo &m, tomo_engine **out)
                     e->rs_groups = std::max(1, std::min(per_cu * e->rs_cus / R.ntiles, e->sxc / 64));
                     e->rs_pb_bytes = (size_t)e->rs_groups * R.ntiles * RS_MAXWIN * 64 * sizeof(rs_u64);
                     e->rs_rb_bytes = (size_t)e->rs_groups * e->np * e->n * 64 * sizeof(rs_u64);
-                    if ((rc = dev_alloc((void **)&e->d_rs_hdr, R.hdr.size() * sizeof(RsHdrD), false, e->stream))) return rc;
-                    if ((rc = dev_alloc((void **)&e->d_rs_cell, R.cell.size() * 4, false, e->stream))) return rc;
-                    if ((rc = dev_alloc((void **)&e->d_rs_ts, R.ts.size(), false, e->stream))) return rc;
-                    if ((rc = dev_alloc((void **)&e->d_rs_rl, R.rl.size() * 2, false, e->stream))) return rc;
-                    if ((rc = dev_alloc((void **)&e->rs_pb, e->rs_pb_bytes, true, e->stream))) return rc;     // tag 0 = never written
-                    if ((rc = dev_alloc((void **)&e->rs_rb, e->rs_rb_bytes, true, e->stream))) return rc;
-                    HIPCHK(hipMemcpy(e->d_rs_hdr, R.hdr.data(), R.hdr.size() * sizeof(RsHdrD), hipMemcpyHostToDevice));
-                    HIPCHK(hipMemcpy(e->d_rs_cell, R.cell.data(), R.cell.size() * 4, hipMemcpyHostToDevice));
-                    HIPCHK(hipMemcpy(e->d_rs_ts, R.ts.data(), R.ts.size(), hipMemcpyHostToDevice));
-                    HIPCHK(hipMemcpy(e->d_rs_rl, R.rl.data(), R.rl.size() * 2, hipMemcpyHostToDevice));
+                    if ((rc = upload_tables(e, {tab(&e->d_rs_hdr, R.hdr), tab(&e->d_rs_cell, R.cell), tab(&e->d_rs_ts, R.ts), tab(&e->d_rs_rl, R.rl)}))) return rc;
+                    if ((rc = dev_alloc(e, GEOMETRY, (void **)&e->rs_pb, e->rs_pb_bytes, true)) || (rc = dev_alloc(e, GEOMETRY, (void **)&e->rs_rb, e->rs_rb_bytes, true))) return rc;     // tag 0 = never written
                     if (!e->rs_abort) { HIPCHK(hipHostMalloc((void **)&e->rs_abort, sizeof(int), hipHostMallocMapped)); *e->rs_abort = 0; }
-                    if ((rc = dev_alloc((void **)&e->d_rs_abort, sizeof(int), true, e->stream))) return rc;
-                    if ((rc = dev_alloc((void **)&e->d_rs_commit, (size_t)(e->sxc / 64) * sizeof(unsigned), true, e->stream))) return rc;
+                    if ((rc = dev_alloc(e, GEOMETRY, (void **)&e->d_rs_abort, sizeof(int), true)) || (rc = dev_alloc(e, GEOMETRY, (void **)&e->d_rs_commit, (size_t)(e->sxc / 64) * sizeof(unsigned), true))) return rc;
                     if (!e->rs_done) { HIPCHK(hipHostMalloc((void **)&e->rs_done, (size_t)(e->sxc / 64) * sizeof(int), hipHostMallocMapped)); }
                     std::memset(e->rs_done, 0, (size_t)(e->sxc / 64) * sizeof(int));
                     e->rs_epoch = 0; e->rs_seq = 0; e->rs_commit_base = 0; e->rs_commit_dirty = false;
@@ -266,10 +208,7 @@ static int finish_create_impl(tomo_engine *e, Coo &m, tomo_engine **out)
         e->fb_ok = t.bp_tile_ok && e->np <= FB_MAX_PROJ;
         e->bl_ok = false;
         if (e->fb_ok) {
-            if ((rc = dev_alloc((void **)&e->d_fb_cell, t.bp_cell.size() * sizeof(uint4), false, e->stream))) return rc;
-            if ((rc = dev_alloc((void **)&e->d_fb_win, t.bp_win.size() * 4, false, e->stream))) return rc;
-            HIPCHK(hipMemcpy(e->d_fb_cell, t.bp_cell.data(), t.bp_cell.size() * sizeof(uint4), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(e->d_fb_win, t.bp_win.data(), t.bp_win.size() * 4, hipMemcpyHostToDevice));
+            if ((rc = upload_tables(e, {tab(&e->d_fb_cell, t.bp_cell), tab(&e->d_fb_win, t.bp_win)}))) return rc;
             release(t.bp_cell);
         }
         lap("build_bp_tiles + upload");
@@ -282,29 +221,20 @@ static int finish_create_impl(tomo_engine *e, Coo &m, tomo_engine **out)
             const size_t nent = (size_t)(t.bl_nbatch + 1) * BL_BATCH;
             e->bl_tiles_z = (e->n + BL_TZ - 1) / BL_TZ;
             e->bl_ntiles = ((e->n + BL_TY - 1) / BL_TY) * e->bl_tiles_z;
-            if ((rc = dev_alloc((void **)&e->d_bl_ent, nent * sizeof(uint4), false, e->stream))) return rc;
-            if ((rc = dev_alloc((void **)&e->d_bl_ptr, t.bl_ptr.size() * 4, false, e->stream))) return rc;
-            if ((rc = dev_alloc((void **)&e->d_bl_win, t.bl_win.size() * 4, false, e->stream))) return rc;
-            HIPCHK(hipMemcpy(e->d_bl_ent, t.bl_ent.get(), nent * sizeof(uint4), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(e->d_bl_ptr, t.bl_ptr.data(), t.bl_ptr.size() * 4, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(e->d_bl_win, t.bl_win.data(), t.bl_win.size() * 4, hipMemcpyHostToDevice));
+            if ((rc = upload_tables(e, {tab(&e->d_bl_ent, t.bl_ent.get(), nent * sizeof(uint4)), tab(&e->d_bl_ptr, t.bl_ptr), tab(&e->d_bl_win, t.bl_win)}))) return rc;
             t.bl_ent.reset();
         }
         release(t.bl_win); release(t.bl_ptr);
     }
     lap("build_bp_lists + upload");
     static_assert(sizeof(Cell) == sizeof(CellD), "cell layout");
-    HIPCHK(hipMemcpy(e->d_cell, t.cell.data(), t.cell.size() * sizeof(CellD), hipMemcpyHostToDevice));
-    g_alloc_meter = nullptr;                       // what follows are fields, not tables
-    if ((rc = dev_alloc((void **)&e->d_scal_own, TOMO_S_COUNT * sizeof(double), true, e->stream))) return rc;
-    if ((rc = dev_alloc((void **)&e->d_part, NPART * sizeof(double), true, e->stream))) return rc;
+    e->table_bytes = e->pool.bytes();              // what follows are fields, not tables
+    if ((rc = dev_alloc(e, ENGINE, (void **)&e->d_scal_own, TOMO_S_COUNT * sizeof(double), true)) || (rc = dev_alloc(e, ENGINE, (void **)&e->d_part, NPART * sizeof(double), true))) return rc;
     e->d_scal = e->d_scal_own;
-    if ((rc = dev_alloc((void **)&e->halo_lo_own, e->npix * sizeof(float), true, e->stream))) return rc;
-    if ((rc = dev_alloc((void **)&e->halo_hi_own, e->npix * sizeof(float), true, e->stream))) return rc;
+    if ((rc = dev_alloc(e, ENGINE, (void **)&e->halo_lo_own, e->npix * sizeof(float), true)) || (rc = dev_alloc(e, ENGINE, (void **)&e->halo_hi_own, e->npix * sizeof(float), true))) return rc;
     e->halo_lo = e->halo_lo_own; e->halo_hi = e->halo_hi_own;
     float *tmp;
-    if ((rc = get_vol(e, TOMO_VOL_RECON, &tmp))) return rc;
-    if ((rc = get_sino(e, &e->sino[TOMO_SINO_B], &tmp))) return rc;
+    if ((rc = get_vol(e, TOMO_VOL_RECON, &tmp)) || (rc = get_sino(e, &e->sino[TOMO_SINO_B], &tmp))) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     *out = e;
     return TOMO_OK;

@@ -59,7 +59,7 @@ static int launch_fp_strip(tomo_engine *e, const float *x, const float *b, float
     const int which = (e->aux && e->stream == e->aux) ? 1 : 0;
     float **slot = which ? &e->fs_part_aux : &e->fs_part;
     if (!*slot) {
-        int rc = dev_alloc((void **)slot, (size_t)std::max<uint32_t>(1, e->fs_nseg) * e->fs_ncp * 64 * sizeof(float), false, e->stream);
+        int rc = dev_alloc(e, GEOMETRY, (void **)slot, (size_t)std::max<uint32_t>(1, e->fs_nseg) * e->fs_ncp * 64 * sizeof(float), false);
         if (rc) return rc;
     }
     for (int c0 = 0; c0 < nchunk; c0 += e->fs_ncp) {
@@ -101,7 +101,7 @@ static int launch_fp_list(tomo_engine *e, const float *x, const float *b, float 
     const int which = (e->aux && e->stream == e->aux) ? 1 : 0;
     float **slot = which ? &e->fl_part_aux : &e->fl_part;
     if (!*slot) {
-        int rc = dev_alloc((void **)slot, (size_t)std::max<uint32_t>(1, e->fl_nseg) * e->fl_ncp * 64 * sizeof(float), false, e->stream);
+        int rc = dev_alloc(e, GEOMETRY, (void **)slot, (size_t)std::max<uint32_t>(1, e->fl_nseg) * e->fl_ncp * 64 * sizeof(float), false);
         if (rc) return rc;
     }
     for (int c0 = 0; c0 < nchunk; c0 += e->fl_ncp) {
@@ -191,7 +191,7 @@ static int launch_fp_all(tomo_engine *e, const float *x, const float *b, float *
     if (!*slot) {
         // sized for both schemes: one pass of ft_ncp chunks, or two halves of a pipelined group each
         size_t chunks = std::max<size_t>(e->ft_ncp, 2 * (size_t)((((e->sxc / 64 + 1) / 2) + 1) & ~1));
-        int rc = dev_alloc((void **)slot, (size_t)std::max<uint32_t>(1, e->ft_nseg) * chunks * 64 * sizeof(float), false, e->stream);
+        int rc = dev_alloc(e, GEOMETRY, (void **)slot, (size_t)std::max<uint32_t>(1, e->ft_nseg) * chunks * 64 * sizeof(float), false);
         if (rc) return rc;
     }
     if (pipe && !e->fp_red_stream[which]) {
@@ -285,7 +285,7 @@ static int launch_sart_seg(tomo_engine *e, const float *x_old, float *x_new, int
 {
     int rc;
     if (!e->seg_partial) {
-        if ((rc = dev_alloc((void **)&e->seg_partial, (size_t)std::max<uint32_t>(1, e->max_items) * e->sx * sizeof(float), true, e->stream))) return rc;
+        if ((rc = dev_alloc(e, GEOMETRY, (void **)&e->seg_partial, (size_t)std::max<uint32_t>(1, e->max_items) * e->sx * sizeof(float), true))) return rc;
     }
     int nchunk = e->sxc / (64 * e->vec);
     uint32_t b0 = e->h_seg_exec_ptr[next], b1 = e->h_seg_exec_ptr[next + 1];
@@ -330,13 +330,13 @@ static int sart_tile_prepare(tomo_engine *e, bool coop)
     }
     const size_t pbytes = (size_t)std::max<uint32_t>(1, e->st_max_ids) * e->sx * sizeof(float);
     if (!e->st_partial) {
-        int rc = dev_alloc((void **)&e->st_partial, pbytes, true, e->stream);
+        int rc = dev_alloc(e, GEOMETRY, (void **)&e->st_partial, pbytes, true);
         if (rc) return rc;
     }
     if (coop && !e->st_partial2) {
-        int rc = dev_alloc((void **)&e->st_partial2, pbytes, true, e->stream);
+        int rc = dev_alloc(e, GEOMETRY, (void **)&e->st_partial2, pbytes, true);
         if (rc) return rc;
-        if ((rc = dev_alloc((void **)&e->st_flags, (size_t)e->n * (e->sxc / 64) * sizeof(uint32_t), true, e->stream))) return rc;
+        if ((rc = dev_alloc(e, GEOMETRY, (void **)&e->st_flags, (size_t)e->n * (e->sxc / 64) * sizeof(uint32_t), true))) return rc;
         // workgroups that start together: the reducer duty is dealt to that many (2 per CU by LDS; any value is correct)
         int per_cu = 0;
         hipDeviceProp_t prop;

@@ -122,7 +122,7 @@ int tomo_tv_partial(tomo_engine *e, int vol, float eps)
         return reduce_end(e, TOMO_S_TV);
     }
     // the march of the gradient kernels without their gradient half: x is read once
-    if (!e->d_part_tv) { if ((rc = dev_alloc((void **)&e->d_part_tv, NPART * sizeof(double), true, e->stream))) return rc; }
+    if (!e->d_part_tv) { if ((rc = dev_alloc(e, ENGINE, (void **)&e->d_part_tv, NPART * sizeof(double), true))) return rc; }
     if ((rc = part_begin(e, e->d_part_tv))) return rc;
     const int yseg = 32;
     if (e->tv_lds == 1 && e->tv_march4 && e->nx % 64 == 0 && e->n % 8 == 0) {
@@ -161,7 +161,7 @@ static int tv_grad_impl(tomo_engine *e, float eps, bool with_tv, float *g_first 
     if ((g_first || g_last) && !(e->tv_lds == 1 && e->tv_recompute)) return fail(TOMO_ERR_STATE, "gradient planes need the recompute form of the TV march (tv_lds = 1, tv_recompute = 1)");
     if (with_tv && e->tv_lds != 8 && e->tv_lds != 1) with_tv = false;
     if (with_tv) {
-        if (!e->d_part_tv) { if ((rc = dev_alloc((void **)&e->d_part_tv, NPART * sizeof(double), true, e->stream))) return rc; }
+        if (!e->d_part_tv) { if ((rc = dev_alloc(e, ENGINE, (void **)&e->d_part_tv, NPART * sizeof(double), true))) return rc; }
         if ((rc = part_begin(e, e->d_part_tv))) return rc;
     }
     {
@@ -283,8 +283,8 @@ static int tv_update_impl(tomo_engine *e, float dPOCS, int clamp, int track_vol,
         float *wl = plane_last, *wh = plane_first;
         if (wrap && own_halo) {
             if (!e->halo_lo_alt) {
-                if ((rc = dev_alloc((void **)&e->halo_lo_alt, e->npix * sizeof(float), true, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->halo_hi_alt, e->npix * sizeof(float), true, e->stream))) return rc;
+                if ((rc = dev_alloc(e, ENGINE, (void **)&e->halo_lo_alt, e->npix * sizeof(float), true))) return rc;
+                if ((rc = dev_alloc(e, ENGINE, (void **)&e->halo_hi_alt, e->npix * sizeof(float), true))) return rc;
             }
             wl = e->halo_lo == e->halo_lo_own ? e->halo_lo_alt : e->halo_lo_own;
             wh = e->halo_hi == e->halo_hi_own ? e->halo_hi_alt : e->halo_hi_own;
@@ -294,8 +294,8 @@ static int tv_update_impl(tomo_engine *e, float dPOCS, int clamp, int track_vol,
         const bool fold = hg_lo && hg_hi && (e->tv_halo_fold < 0 ? e->sxc >= 128 : e->tv_halo_fold != 0) && own_halo && !wrap && e->tv_tz != 4 && e->tv_march4;
         if (fold) {
             if (!e->halo_lo_alt) {
-                if ((rc = dev_alloc((void **)&e->halo_lo_alt, e->npix * sizeof(float), true, e->stream))) return rc;
-                if ((rc = dev_alloc((void **)&e->halo_hi_alt, e->npix * sizeof(float), true, e->stream))) return rc;
+                if ((rc = dev_alloc(e, ENGINE, (void **)&e->halo_lo_alt, e->npix * sizeof(float), true))) return rc;
+                if ((rc = dev_alloc(e, ENGINE, (void **)&e->halo_hi_alt, e->npix * sizeof(float), true))) return rc;
             }
             up.hg_lo = hg_lo; up.hg_hi = hg_hi;
             up.ho_lo = e->halo_lo == e->halo_lo_own ? e->halo_lo_alt : e->halo_lo_own;

@@ -9,6 +9,7 @@
 #include "sart_resident.hip.h"
 #include "sysmat.h"
 #include "resident.h"
+#include "dev_pool.h"
 
 #include <dlfcn.h>
 #if __has_include(<rccl/rccl.h>)
@@ -111,6 +112,10 @@ struct ChainHelper {
         }
     }
 };
+
+// the allocator of every engine's DevPool: the only raw device allocation and release of the engine
+static int pool_alloc(void **p, size_t bytes) { HIPCHK(hipMalloc(p, bytes)); return TOMO_OK; }
+static void pool_free(void *p) { (void)hipFree(p); }
 
 struct CommRef;
 struct tomo_engine;
@@ -322,17 +327,19 @@ struct tomo_engine {
     std::mutex prof_mu;
     size_t vol_elems() const { return (size_t)npix * sx; }
     size_t sino_elems() const { return (size_t)nrows * sx; }
+    // every device allocation of the engine (dev_pool.h).  Caller-bound buffers and the aliases of owned ones (d_scal, halo_lo / halo_hi,
+    // fgp_lo ..., gnorm_override) are never registered.
+    DevPool pool{pool_alloc, pool_free};
 };
 
 static inline double *gnorm_ptr(const tomo_engine *e) { return e->gnorm_override ? e->gnorm_override : e->d_scal + e->gnorm_slot; }
 
-// (bytes handed out while an engine is being created are counted for it: tomo_get_option "table_kib")
-static thread_local size_t *g_alloc_meter = nullptr;
-static int dev_alloc(void **p, size_t bytes, bool zero, hipStream_t st)
+constexpr DevPool::Life GEOMETRY = DevPool::GEOMETRY, COMM = DevPool::COMM, ENGINE = DevPool::ENGINE;
+// *p = a new device buffer of the engine, owned by its pool; zero: cleared on the engine's stream
+static int dev_alloc(tomo_engine *e, DevPool::Life life, void **p, size_t bytes, bool zero)
 {
-    HIPCHK(hipMalloc(p, bytes ? bytes : 4));
-    if (g_alloc_meter) *g_alloc_meter += bytes;
-    if (zero) HIPCHK(hipMemsetAsync(*p, 0, bytes ? bytes : 4, st));
+    if (int rc = e->pool.alloc(life, p, bytes)) return rc;
+    if (zero) HIPCHK(hipMemsetAsync(*p, 0, bytes ? bytes : 4, e->stream));
     return TOMO_OK;
 }
 
@@ -369,10 +376,7 @@ static int get_vol_ro(tomo_engine *e, int id, float **out)
 {
     if (id < 0 || id >= TOMO_VOL_SLOTS) return fail(TOMO_ERR_ARG, "bad volume id");
     if (id == TOMO_VOL_RECON_OLD && e->old_is_recon) id = TOMO_VOL_RECON;     // read-only view of the same content
-    if (!e->vol[id]) {
-        int rc = dev_alloc((void **)&e->vol[id], e->vol_elems() * sizeof(float), true, e->stream);
-        if (rc) return rc;
-    }
+    if (!e->vol[id]) { int rc = dev_alloc(e, ENGINE, (void **)&e->vol[id], e->vol_elems() * sizeof(float), true); if (rc) return rc; }
     *out = e->vol[id];
     return TOMO_OK;
 }
@@ -393,10 +397,7 @@ static int get_vol(tomo_engine *e, int id, float **out)
 static int get_sino(tomo_engine *e, float **slot, float **out)
 {
     if (slot == &e->sino[TOMO_SINO_G]) g_clear(e);      // whoever asks for G may overwrite it
-    if (!*slot) {
-        int rc = dev_alloc((void **)slot, e->sino_elems() * sizeof(float), true, e->stream);
-        if (rc) return rc;
-    }
+    if (!*slot) { int rc = dev_alloc(e, GEOMETRY, (void **)slot, e->sino_elems() * sizeof(float), true); if (rc) return rc; }
     *out = *slot;
     return TOMO_OK;
 }
@@ -409,10 +410,7 @@ static int sino_slot(tomo_engine *e, int id, float **out)
 
 static int get_scratch(tomo_engine *e, float **slot, float **out)
 {
-    if (!*slot) {
-        int rc = dev_alloc((void **)slot, e->vol_elems() * sizeof(float), true, e->stream);
-        if (rc) return rc;
-    }
+    if (!*slot) { int rc = dev_alloc(e, ENGINE, (void **)slot, e->vol_elems() * sizeof(float), true); if (rc) return rc; }
     *out = *slot;
     return TOMO_OK;
 }
@@ -428,8 +426,8 @@ static int order_after_async(tomo_engine *e)
 static int ensure_stage(tomo_engine *e, size_t bytes)
 {
     if (e->stage_bytes >= bytes) return TOMO_OK;
-    if (e->stage) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipFree(e->stage)); e->stage = nullptr; }
-    HIPCHK(hipMalloc((void **)&e->stage, bytes));
+    if (e->stage) { HIPCHK(hipStreamSynchronize(e->stream)); e->pool.release(e->stage); e->stage_bytes = 0; }
+    if (int rc = dev_alloc(e, ENGINE, (void **)&e->stage, bytes, false)) return rc;
     e->stage_bytes = bytes;
     return TOMO_OK;
 }
