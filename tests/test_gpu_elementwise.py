@@ -17,6 +17,9 @@ Geometry table (angles in degrees; N rays; Nx slices):
   lin70       linspace(-70, 70, 9)                32   128  list strip tile rows     list tile all     control, one 128-slice piece
   lin70w      linspace(-70, 70, 9)                32   320  tile with 1 / 2 / 3      -                 5 chunks of 64: 5 / 3 / 2 passes
                                                             chunks per pass                            (asserted by the launch log)
+  lin70x      linspace(-70, 70, 9)                32   256  (ART chain only)         -                 4 chunks of 64: the per-row kernels at
+                                                                                                       vector width 4 where the slab is ONE
+                                                                                                       chain of launches (two halves: width 2)
   lin70       (list asked for on Nx = 192, 129)   32        strip (fallback)         tile (fallback)   no whole 128-slice pieces
   axes45      -90 -67 -45 -20 0 20 45 67 90       33   128  list strip tile rows     list tile all     exact 0 / +-45 / +-90, odd N
   half180     0 ... 180 step 1 (181 angles)       31   128  list strip tile rows     list tile all     beyond +-90, many strip passes
@@ -31,9 +34,10 @@ Geometry table (angles in degrees; N rays; Nx slices):
 
 SART (one sweep, the angles in the order given): resident (N % 8 == 0; one launch, no fallback) / tile / angle on lin70, axes45
 (angle, tile), dose_sym, repeat, neg150, and resident at N = 512.  tomo_sirt, Landweber and Cimmino on lin70, axes45, dose_sym; the
-ART chain there in its tile-fused and per-angle forms (the launch log tells them apart).  tv_gd(1) with the kernels k_tv_march4
-(tz 8), k_tv_grad_reg<8> and k_tv_grad_reg<4>, and FGP with 2 and 3 iterations in each form (pair, fused, unfused), on N in
-{8, 31, 32, 33, 96} x Nx in {1, 63, 64, 65, 129} (the predicated edge forms: nx % 64 != 0, n % 8 != 0).
+ART chain there and on lin70x in its tile-fused and per-angle forms (the launch log tells them apart).  tv_gd(1) with the kernels
+k_tv_march4 (tz 8; its update pass also streamed, tracked and both), k_tv_grad_reg<8> and k_tv_grad_reg<4>, and FGP with 2 and 3
+iterations in each form (pair, fused, unfused), on N in {8, 31, 32, 33, 96} x Nx in {1, 63, 64, 65, 129} (the predicated edge forms:
+nx % 64 != 0, n % 8 != 0).
 """
 import ctypes
 
@@ -43,7 +47,7 @@ import pytest
 import oracle
 import ref64
 from tomo_tv_amd import _lib
-from tomo_tv_amd._lib import VOL_ORIGINAL, VOL_RECON
+from tomo_tv_amd._lib import S_DIFF, VOL_ORIGINAL, VOL_RECON, VOL_TEMP
 from tomo_tv_amd.engine import ctvlib, system_matrix, tomoengine
 
 pytestmark = pytest.mark.gpu
@@ -57,6 +61,7 @@ BP_CODE = {"all": BP_ALL, "tile": BP_TILE, "list": BP_LIST}
 GEOM = {
     "lin70": (np.linspace(-70, 70, 9), 32, 128),
     "lin70w": (np.linspace(-70, 70, 9), 32, 320),
+    "lin70x": (np.linspace(-70, 70, 9), 32, 256),
     "axes45": (np.array([-90.0, -67.0, -45.0, -20.0, 0.0, 20.0, 45.0, 67.0, 90.0]), 33, 128),
     "half180": (np.arange(0.0, 181.0, 1.0), 31, 128),
     "p193": (np.linspace(-80, 80, 193), 32, 128),
@@ -300,7 +305,9 @@ def test_sirt_landweber_cimmino_step_elementwise(gpu, monkeypatch, gid):
         ref64.assert_within(kind, c.get_volume(), ref, bound)
 
 
-ART_CASES = [(g, v) for g in STEP_GEOM for v in ("tile", "angle")]
+# tile1: the tile-fused form as ONE chain of launches ("sart_streams" = 1; by default a slab of an even number of 64-slice chunks
+# runs as two half-slab chains, whose per-row kernels take the vector width that divides the half: 2 at 256 slices, 4 as one chain)
+ART_CASES = [(g, v) for g in STEP_GEOM for v in ("tile", "angle")] + [("lin70x", "tile1"), ("lin70x", "angle")]
 
 
 @pytest.mark.parametrize("gid,variant", ART_CASES, ids=[f"{g}-art_chain_{v}" for g, v in ART_CASES])
@@ -314,13 +321,17 @@ def test_art_chain_elementwise(gpu, gid, variant):
     c = ctvlib(Nx, N, M.P)
     c.load_A(system_matrix(N, ang))
     c.set_option("art_chain", 1)
-    c.set_option("art_tile", 1 if variant == "tile" else 0)
+    c.set_option("art_tile", 0 if variant == "angle" else 1)
+    if variant == "tile1":
+        c.set_option("sart_streams", 1)
     assert c.get_option("art_chain_ready") == 1
     c.set_tilt_series(b)
     c.set_volume(x, VOL_RECON)
     c.row_inner_product()
     fused = launches(c, _lib.K_SART_FUSED, lambda: c.ART(0.6))
-    if variant == "tile":
+    if variant == "tile1":
+        assert fused == M.P - 1, fused
+    elif variant == "tile":
         assert fused > 0 and fused % (M.P - 1) == 0, fused
     else:
         assert fused == 0
@@ -387,6 +398,10 @@ def test_resident_sart_at_the_headline_geometry(gpu, monkeypatch, big512):
 TV_CASES = [(8, 1), (31, 63), (32, 64), (33, 65), (96, 129), (32, 129), (31, 1)]
 # (kernel that runs, tv_march4, tv_tz): with tv_tz = 4 both passes run k_tv_grad_reg<4> whatever tv_march4 says
 TV_OPTS = [("march4_tz8", 1, 8), ("reg_tz8", 0, 8), ("reg_tz4", 1, 4)]
+# ... and (sart_nt, tracked), the other instances of the march's update pass: sart_nt = 1 streams its accesses at any slab size (-1: by
+# size, none of these); tracked: tv_gd_tracked, whose last update pass also forms the step norm and writes the snapshot
+TV_UPDATE_OPTS = [o + (-1, False) for o in TV_OPTS] + \
+                 [("march4_tz8_nt", 1, 8, 1, False), ("march4_tz8_tracked", 1, 8, -1, True), ("march4_tz8_nt_tracked", 1, 8, 1, True)]
 
 
 def _tv_input(Nx, N):
@@ -402,14 +417,23 @@ def test_tv_gd_elementwise(gpu, N, Nx):
     orc.recon[:] = x
     orc.tv_gd(1, dpocs)
     t64 = ref64.tv_gd(x, 1, dpocs, eps)
-    for name, march4, tz in TV_OPTS:
+    for name, march4, tz, nt, tracked in TV_UPDATE_OPTS:
         t = tomoengine(Nx, N, np.array([0.3]))
         t.tv_eps = eps
         t.set_option("tv_march4", march4)
         t.set_option("tv_tz", tz)
+        t.set_option("sart_nt", nt)
         t.set_volume(x, VOL_RECON)
-        t.tv_gd(1, dpocs)
-        ref64.assert_seq(f"tv_gd {name}", t.get_volume(), orc.recon, t64)
+        if tracked:                                        # the snapshot (TEMP) holds the volume before the step
+            t.set_volume(x, VOL_TEMP)
+            t.tv_gd_tracked(1, dpocs)
+        else:
+            t.tv_gd(1, dpocs)
+        got = t.get_volume()
+        ref64.assert_seq(f"tv_gd {name}", got, orc.recon, t64)
+        if tracked:                                        # ... then the new volume, and S_DIFF the squared norm of the step taken
+            assert np.array_equal(t.get_volume(VOL_TEMP), got), name
+            ref64.assert_scalar(f"S_DIFF tv_gd {name}", t._scalar(S_DIFF), *ref64.sqdiff(got, x))
 
 
 @pytest.mark.parametrize("iters", [2, 3])

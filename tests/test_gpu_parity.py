@@ -741,15 +741,19 @@ def _independent_fbp_taps(n, name):
     return taps
 
 
-@pytest.mark.parametrize("name", ["ram-lak", "shepp-logan", "hamming", "cosine", "parzen", "lanczos", "triangular", "gaussian",
-                                  "blackman", "nuttall", "blackman-harris", "kaiser"])
-def test_wbp_all_twelve_filters_against_independent_taps(gpu, name):
+# 2 slices: the row filter and the voxel-driven back projection at vector width 1; 128 and 256 slices (one filter): widths 2 and 4
+WBP_CASES = [(name, 2) for name in ("ram-lak", "shepp-logan", "hamming", "cosine", "parzen", "lanczos", "triangular", "gaussian",
+                                    "blackman", "nuttall", "blackman-harris", "kaiser")] + [("hamming", 128), ("hamming", 256)]
+
+
+@pytest.mark.parametrize("name,Nx", WBP_CASES, ids=[n if nx == 2 else f"{n}-nx{nx}" for n, nx in WBP_CASES])
+def test_wbp_all_twelve_filters_against_independent_taps(gpu, name, Nx):
     """Every filter name of tomofusion/pytvlib.py:33-36 through TomoGPU.wbp's path, against recon = pi/P A^T (h * b) evaluated
     with taps built in THIS file (explicit cosine sums) and the oracle's A^T (tomoengine.cpp:317-347; ASTRA's own filter
     construction is absent: parity unpinned, the definition is DESIGN.md's)."""
     from tomo_tv_amd import pytvlib as ptl
     assert name in ptl.wbp_filters()
-    N, P, Nx = 48, 24, 2
+    N, P = 48, 24
     ang = np.linspace(-90, 82.5, P)
     x = ellipsoids(Nx, N, seed=6, k=5)
     dev = tomoengine(Nx, N, np.deg2rad(ang))

@@ -322,12 +322,8 @@ int tomo_sirt_cimmino(tomo_engine *e, int vol, float beta, int niter)
     NEED(e);
     float *x, *r; int rc;
     if ((rc = get_vol(e, vol, &x)) || (rc = get_sino(e, &e->sino[TOMO_SINO_R], &r))) return rc;
-    const float *rs = e->d_rowsum;
     for (int it = 0; it < niter; ++it) {
-        e->d_rowsum = e->d_rowinner;                     // the FP epilogue reads its per-row factor from this argument
-        rc = launch_fp_all<FP_RESID_MUL>(e, x, e->sino[TOMO_SINO_B], r);
-        e->d_rowsum = const_cast<float *>(rs);
-        if (rc) return rc;
+        if ((rc = launch_fp_all<FP_RESID_MUL>(e, x, e->sino[TOMO_SINO_B], r, e->d_rowinner))) return rc;   // the epilogue's per-row factor: |A_i|^2
         if ((rc = launch_bp_all(e, x, r, nullptr, 1.f, beta / (float)e->nrows, 1))) return rc;
     }
     return TOMO_OK;
@@ -366,7 +362,8 @@ static int launch_sart_resident(tomo_engine *e, float *x, float beta, int64_t st
 {
     failed.clear();
     if (steps > (int64_t)1 << 24) return fail(TOMO_ERR_ARG, "too many SART steps in one call");
-    const int c0 = e->sub_nc ? e->sub_c0 : 0, nc = e->sub_nc ? e->sub_nc : e->sxc / 64;
+    const Chunks all = chunks64(e, whole(e));
+    const int c0 = all.c0, nc = all.n;
     const int groups = std::max(1, std::min(e->rs_groups, nc)), rounds = (nc + groups - 1) / groups;
     {   // the angle of every step, on the device (an unchanged sequence stays where it is)
         std::vector<int> seq((size_t)steps);
@@ -600,36 +597,22 @@ int tomo_art_order(tomo_engine *e, float beta, const int32_t *order_host)
         float *d, *a; int rc;
         if ((rc = get_sino(e, &e->sino[TOMO_SINO_G], &d)) || (rc = get_sino(e, &e->sino[TOMO_SINO_R], &a))) return rc;
         const float *b = e->sino[TOMO_SINO_B];
-        int nchunk = e->sxc / (64 * e->vec);
-        int ngroups = (int)((e->npix + BP_PPW - 1) / BP_PPW);
-        dim3 bgrid((unsigned)(((int64_t)ngroups * nchunk + 3) / 4));
         if (e->art_tile && e->sart_tile && e->st_ok && e->np >= 1) {
             // the same fused steps as the SART sweep: FP(a0); [BP_art(a_k-1) + FP(a_k)] ...; BP_art(a_last), the residual rows of
             // each angle formed by k_art_chain from the tile step's row sums.  Per angle 228 instead of 323 us at 512^3.
             if ((rc = sart_tile_prepare(e, false))) return rc;
             e->cur_b = const_cast<float *>(b);
-            const int np = e->np, strm = slab_streams(e) ? 1 : 0;
+            const int np = e->np;
             auto chain = [&](const Sub &sb) -> int {        // one sub-slab's (or the whole slab's) chain of launches
-                const int c64 = sb.nc ? sb.c0 : 0, nc64 = sb.nc ? sb.nc : e->sxc / 64;
+                const Chunks ch = chunks64(e, sb);
                 for (int i = 0; i < np; ++i) {
                     int rc2 = i == 0 ? launch_sart_tile<false, true>(e, sb, x, 0, 0, a, beta, nullptr, true, -1, d)
                                      : launch_sart_tile<true, true>(e, sb, x, i - 1, i, a, beta, nullptr, true, i, d);
                     if (rc2) return rc2;
-                    hipLaunchKernelGGL(k_art_chain, dim3((unsigned)nc64), dim3(64 * ART_CW), 0, sb.stream, d, b, e->d_rowinner, e->d_rowcross, a, beta, i * e->n, e->n, e->sx, c64);
+                    hipLaunchKernelGGL(k_art_chain, dim3((unsigned)ch.n), dim3(64 * ART_CW), 0, sb.stream, d, b, e->d_rowinner, e->d_rowcross, a, beta, i * e->n, e->n, e->sx, ch.c0);
                     LAUNCHCHK();
                 }
-                const int last = np - 1, vec = sub_vec(e, sb);
-                const CellD *cell = e->d_cell + (size_t)last * e->npix;
-                const float *ai = a + (size_t)last * e->n * e->sx;
-                const int nch = nc64 / vec, ch0 = c64 / vec;
-                dim3 grid((unsigned)(((int64_t)ngroups * nch + 3) / 4));
-                switch (vec) {
-                case 4: hipLaunchKernelGGL((k_bp_art<4, BP_PPW>), grid, dim3(256), 0, sb.stream, x, cell, ai, beta, (int)e->npix, e->sx, ngroups, nch, strm, ch0); break;
-                case 2: hipLaunchKernelGGL((k_bp_art<2, BP_PPW>), grid, dim3(256), 0, sb.stream, x, cell, ai, beta, (int)e->npix, e->sx, ngroups, nch, strm, ch0); break;
-                default: hipLaunchKernelGGL((k_bp_art<1, BP_PPW>), grid, dim3(256), 0, sb.stream, x, cell, ai, beta, (int)e->npix, e->sx, ngroups, nch, strm, ch0); break;
-                }
-                LAUNCHCHK();
-                return TOMO_OK;
+                return launch_bp_art(e, sb, x, np - 1, a, beta);
             };
             if ((rc = run_chains(e, chain))) return rc;
             return tomo_positivity(e, TOMO_VOL_RECON);
@@ -638,14 +621,7 @@ int tomo_art_order(tomo_engine *e, float beta, const int32_t *order_host)
             if ((rc = launch_fp<FP_STORE>(e, x, i * e->n, e->n, nullptr, d))) return rc;
             hipLaunchKernelGGL(k_art_chain, dim3((unsigned)(e->sx / 64)), dim3(64 * ART_CW), 0, e->stream, d, b, e->d_rowinner, e->d_rowcross, a, beta, i * e->n, e->n, e->sx, 0);
             LAUNCHCHK();
-            const CellD *cell = e->d_cell + (size_t)i * e->npix;
-            const float *ai = a + (size_t)i * e->n * e->sx;
-            switch (e->vec) {
-            case 4: hipLaunchKernelGGL((k_bp_art<4, BP_PPW>), bgrid, dim3(256), 0, e->stream, x, cell, ai, beta, (int)e->npix, e->sx, ngroups, nchunk, slab_streams(e) ? 1 : 0, 0); break;
-            case 2: hipLaunchKernelGGL((k_bp_art<2, BP_PPW>), bgrid, dim3(256), 0, e->stream, x, cell, ai, beta, (int)e->npix, e->sx, ngroups, nchunk, slab_streams(e) ? 1 : 0, 0); break;
-            default: hipLaunchKernelGGL((k_bp_art<1, BP_PPW>), bgrid, dim3(256), 0, e->stream, x, cell, ai, beta, (int)e->npix, e->sx, ngroups, nchunk, slab_streams(e) ? 1 : 0, 0); break;
-            }
-            LAUNCHCHK();
+            if ((rc = launch_bp_art(e, whole(e), x, i, a, beta))) return rc;
         }
         return tomo_positivity(e, TOMO_VOL_RECON);
     }
@@ -756,11 +732,9 @@ int tomo_fbp(tomo_engine *e, const float *taps_host, float scale, int apply_posi
     int nchunk = e->sxc / (64 * e->vec);
     int64_t waves = e->nrows * nchunk;
     dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-    switch (e->vec) {
-    case 4: hipLaunchKernelGGL((k_filter_rows<4>), grid, block, 0, e->stream, b, g, e->fbp_h, e->n, (int)e->nrows, e->sx, nchunk); break;
-    case 2: hipLaunchKernelGGL((k_filter_rows<2>), grid, block, 0, e->stream, b, g, e->fbp_h, e->n, (int)e->nrows, e->sx, nchunk); break;
-    default: hipLaunchKernelGGL((k_filter_rows<1>), grid, block, 0, e->stream, b, g, e->fbp_h, e->n, (int)e->nrows, e->sx, nchunk); break;
-    }
+    with_vec(e->vec, [&](auto V) {
+        hipLaunchKernelGGL((k_filter_rows<V()>), grid, block, 0, e->stream, b, g, e->fbp_h, e->n, (int)e->nrows, e->sx, nchunk);
+    });
     LAUNCHCHK();
     return launch_bp_all(e, x, g, nullptr, 0.f, scale, apply_positivity ? 1 : 0);
 }

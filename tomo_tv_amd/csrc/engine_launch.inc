@@ -1,81 +1,109 @@
 // engine_launch.inc -- part of tomo_engine.hip (ONE translation unit: the kernels are templates and asm blocks in headers; the host side is
 // split by topic into files that tomo_engine.hip includes in order).  This part: which kernel family runs (select_forms) and the launch helpers of the projectors, the SART steps and the all-angle back projection.
 
-// ---- projector launches -------------------------------------------------------------------------------------
-// vec_override: 0 = wide form (64*vec slices per workgroup, scalar table walk); 16 / 32 = narrow-chunk form with that
-// many lanes per ray (k_fp_rows_g)
-template <int MODE>
-static int launch_fp(tomo_engine *e, const float *x, int row0, int nrows, const float *b, float *out, int lpr = 0)
+// ---- run-time value -> template argument ----------------------------------------------------------------------
+// The ONE way a run-time value picks a kernel instantiation: f is called with a std::integral_constant of the value (the last
+// of Vs where v is none of them) and launches inside, reading it as V().  Nest only parameters whose every combination exists.
+template <int V0, int... Vs, class F>
+static void with_int(int v, F &&f)
 {
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V0>{});
+    else if (v == V0) f(std::integral_constant<int, V0>{});
+    else with_int<Vs...>(v, f);
+}
+template <class F> static void with_vec(int vec, F &&f) { with_int<4, 2, 1>(vec, f); }
+template <class F> static void with_flag(bool b, F &&f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+
+// the 64-slice chunks a launch covers: the sub-slab's, else the whole slab's
+struct Chunks { int n, c0; };
+static Chunks chunks64(const tomo_engine *e, const Sub &sb) { return sb.nc ? Chunks{sb.nc, sb.c0} : Chunks{e->sxc / 64, 0}; }
+
+// ---- projector launches -------------------------------------------------------------------------------------
+// lpr: 0 = wide form (64*vec slices per workgroup, scalar table walk); 16 / 32 = narrow-chunk form with that
+// many lanes per ray (k_fp_rows_g).  rowfac: the per-row factor of the epilogue.  Null means "the row sums" (d_rowsum), here and in
+// launch_fp_all: a caller that names another table passes one that exists (d_rowinner is uploaded with the geometry).
+template <int MODE>
+static int launch_fp(tomo_engine *e, const float *x, int row0, int nrows, const float *b, float *out, int lpr = 0, const float *rowfac = nullptr)
+{
+    if (!rowfac) rowfac = e->d_rowsum;
     if (lpr == 16 || lpr == 32) {
         int R = 64 / lpr;
         int nchunk = e->sxc / (lpr * 4);
         int64_t waves = (int64_t)((nrows + R - 1) / R) * nchunk;
         dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-        if (lpr == 16) hipLaunchKernelGGL((k_fp_rows_g<16, MODE>), grid, block, 0, e->stream, x, e->d_rptr, e->d_rent, b, e->d_rowsum, out, e->d_part, row0, nrows, e->sx, nchunk);
-        else hipLaunchKernelGGL((k_fp_rows_g<32, MODE>), grid, block, 0, e->stream, x, e->d_rptr, e->d_rent, b, e->d_rowsum, out, e->d_part, row0, nrows, e->sx, nchunk);
+        with_int<16, 32>(lpr, [&](auto L) {
+            hipLaunchKernelGGL((k_fp_rows_g<L(), MODE>), grid, block, 0, e->stream, x, e->d_rptr, e->d_rent, b, rowfac, out, e->d_part, row0, nrows, e->sx, nchunk);
+        });
         LAUNCHCHK();
         return TOMO_OK;
     }
     int vec = e->vec;
     int nchunk = e->sxc / (64 * vec);
     dim3 grid((unsigned)((int64_t)nrows * nchunk)), block(256);
-    switch (vec) {
-    case 4: hipLaunchKernelGGL((k_fp_rows<4, MODE>), grid, block, 0, e->stream, x, e->d_rptr, e->d_rent, b, e->d_rowsum, out, e->d_part, row0, nrows, e->sx); break;
-    case 2: hipLaunchKernelGGL((k_fp_rows<2, MODE>), grid, block, 0, e->stream, x, e->d_rptr, e->d_rent, b, e->d_rowsum, out, e->d_part, row0, nrows, e->sx); break;
-    default: hipLaunchKernelGGL((k_fp_rows<1, MODE>), grid, block, 0, e->stream, x, e->d_rptr, e->d_rent, b, e->d_rowsum, out, e->d_part, row0, nrows, e->sx); break;
-    }
+    with_vec(vec, [&](auto V) {
+        hipLaunchKernelGGL((k_fp_rows<V(), MODE>), grid, block, 0, e->stream, x, e->d_rptr, e->d_rent, b, rowfac, out, e->d_part, row0, nrows, e->sx);
+    });
     LAUNCHCHK();
     return TOMO_OK;
 }
 
 template <int MODE>
 static void launch_fp_reduce(tomo_engine *e, hipStream_t rs, const float *part, const uint32_t *rsptr, const uint32_t *rsidx, const float *b,
-                             float *out, int c0, int ncp)
+                             const float *rowfac, float *out, int c0, int ncp)
 {
     int lpr = (ncp % 4 == 0) ? 64 : (ncp % 2 == 0) ? 32 : 16;
     int64_t items = (int64_t)e->nrows * (ncp * 16 / lpr);
     int64_t waves = (items + 64 / lpr - 1) / (64 / lpr);
     dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-    switch (lpr) {
-    case 64: hipLaunchKernelGGL((k_fp_tile_reduce<64, MODE>), grid, block, 0, rs, part, rsptr, rsidx, b, e->d_rowsum, out, e->d_part, (int)e->nrows, e->sx, c0, ncp); break;
-    case 32: hipLaunchKernelGGL((k_fp_tile_reduce<32, MODE>), grid, block, 0, rs, part, rsptr, rsidx, b, e->d_rowsum, out, e->d_part, (int)e->nrows, e->sx, c0, ncp); break;
-    default: hipLaunchKernelGGL((k_fp_tile_reduce<16, MODE>), grid, block, 0, rs, part, rsptr, rsidx, b, e->d_rowsum, out, e->d_part, (int)e->nrows, e->sx, c0, ncp); break;
-    }
+    with_int<64, 32, 16>(lpr, [&](auto L) {
+        hipLaunchKernelGGL((k_fp_tile_reduce<L(), MODE>), grid, block, 0, rs, part, rsptr, rsidx, b, rowfac, out, e->d_part, (int)e->nrows, e->sx, c0, ncp);
+    });
+}
+
+// Chunks per pass of an all-angle FP whose scratch takes nseg partial rows per 64-slice chunk: what "ft_scratch_cap" holds (or the
+// forced count), rounded down to whole 64- or 32-lane spans of the reduce; pairs: whole 128-slice pieces, a forced count too.
+static int plan_ncp(const tomo_engine *e, uint32_t nseg, bool pairs)
+{
+    const int nchunk = e->sxc / 64, least = pairs ? 2 : 1;
+    const size_t per_chunk = (size_t)std::max<uint32_t>(1, nseg) * 64 * sizeof(float);
+    int ncp = (int)std::min<size_t>(nchunk, std::max<size_t>(least, e->ft_scratch_cap / per_chunk));
+    if (e->ft_ncp_forced > 0) ncp = std::min(nchunk, std::max(least, e->ft_ncp_forced));
+    if (e->ft_ncp_forced > 0 && !pairs) return ncp;
+    if (ncp >= 4) return ncp & ~3;
+    return pairs || ncp >= 2 ? 2 : ncp;
+}
+
+// That scratch: one buffer per stream that projects (fp_which = 1: the second stream), `chunks` chunks large, allocated on first use.
+static int fp_which(const tomo_engine *e) { return (e->aux && e->stream == e->aux) ? 1 : 0; }
+static int fp_scratch(tomo_engine *e, float **slot, uint32_t nseg, size_t chunks)
+{
+    if (*slot) return TOMO_OK;
+    return dev_alloc(e, GEOMETRY, (void **)slot, (size_t)std::max<uint32_t>(1, nseg) * chunks * 64 * sizeof(float), false);
 }
 
 // all-angle FP, sheared-strip form (k_fp_strip + k_fp_tile_reduce on the strips' row lists)
 template <int MODE>
-static int launch_fp_strip(tomo_engine *e, const float *x, const float *b, float *out)
+static int launch_fp_strip(tomo_engine *e, const float *x, const float *b, float *out, const float *rowfac)
 {
     const int nchunk = e->sxc / 64;
-    if (!e->fs_ncp) {
-        size_t per_chunk = (size_t)std::max<uint32_t>(1, e->fs_nseg) * 64 * sizeof(float);
-        int ncp = (int)std::min<size_t>(nchunk, std::max<size_t>(1, e->ft_scratch_cap / per_chunk));
-        if (e->ft_ncp_forced > 0) ncp = std::min(nchunk, e->ft_ncp_forced);
-        else if (ncp >= 4) ncp &= ~3; else if (ncp >= 2) ncp &= ~1;
-        e->fs_ncp = ncp;
-    }
-    const int which = (e->aux && e->stream == e->aux) ? 1 : 0;
-    float **slot = which ? &e->fs_part_aux : &e->fs_part;
-    if (!*slot) {
-        int rc = dev_alloc(e, GEOMETRY, (void **)slot, (size_t)std::max<uint32_t>(1, e->fs_nseg) * e->fs_ncp * 64 * sizeof(float), false);
-        if (rc) return rc;
-    }
+    if (!e->fs_ncp) e->fs_ncp = plan_ncp(e, e->fs_nseg, false);
+    float **slot = fp_which(e) ? &e->fs_part_aux : &e->fs_part;
+    if (int rc = fp_scratch(e, slot, e->fs_nseg, e->fs_ncp)) return rc;
+    float *part = *slot;
     for (int c0 = 0; c0 < nchunk; c0 += e->fs_ncp) {
         const int ncp = std::min(e->fs_ncp, nchunk - c0);
         {
             ProfScope ps(e, TOMO_K_FP_TILE);
             dim3 grid((unsigned)(8 * ((e->fs_nitems + 7) / 8) * ncp)), block(FS_THREADS);
-#define FS_LAUNCH(KK) hipLaunchKernelGGL((k_fp_strip<KK>), grid, block, 0, e->stream, x, e->d_fs_items, e->d_fs_orient, e->d_fs_shift, e->d_fs_cnt, \
-                                         e->d_fs_gstart, e->d_fs_gseg0, e->d_fs_ent, *slot, e->n, e->sx, e->fs_nitems, c0, ncp, e->d_fs_zero)
-            if (e->fs_kused <= 8) FS_LAUNCH(8); else if (e->fs_kused <= 12) FS_LAUNCH(12); else FS_LAUNCH(16);
-#undef FS_LAUNCH
+            with_int<8, 12, 16>(e->fs_kused <= 8 ? 8 : e->fs_kused <= 12 ? 12 : 16, [&](auto K) {
+                hipLaunchKernelGGL((k_fp_strip<K()>), grid, block, 0, e->stream, x, e->d_fs_items, e->d_fs_orient, e->d_fs_shift, e->d_fs_cnt,
+                                   e->d_fs_gstart, e->d_fs_gseg0, e->d_fs_ent, part, e->n, e->sx, e->fs_nitems, c0, ncp, e->d_fs_zero);
+            });
             LAUNCHCHK();
         }
         {
             ProfScope ps(e, TOMO_K_FP_REDUCE);
-            launch_fp_reduce<MODE>(e, e->stream, *slot, e->d_fs_rsptr, e->d_fs_rsidx, b, out, c0, ncp);
+            launch_fp_reduce<MODE>(e, e->stream, part, e->d_fs_rsptr, e->d_fs_rsidx, b, rowfac, out, c0, ncp);
             LAUNCHCHK();
         }
     }
@@ -84,38 +112,29 @@ static int launch_fp_strip(tomo_engine *e, const float *x, const float *b, float
 
 // all-angle FP, sheared strips as wave-uniform entry lists (k_fp_list + k_fp_tile_reduce on the lists' row lists)
 template <int MODE>
-static int launch_fp_list(tomo_engine *e, const float *x, const float *b, float *out)
+static int launch_fp_list(tomo_engine *e, const float *x, const float *b, float *out, const float *rowfac)
 {
     const int nchunk = e->sxc / 64;
-    if (!e->fl_ncp) {
-        size_t per_chunk = (size_t)std::max<uint32_t>(1, e->fl_nseg) * 64 * sizeof(float);
-        int ncp = (int)std::min<size_t>(nchunk, std::max<size_t>(2, e->ft_scratch_cap / per_chunk));
-        if (e->ft_ncp_forced > 0) ncp = std::min(nchunk, std::max(2, e->ft_ncp_forced));
-        if (ncp >= 4) ncp &= ~3; else ncp = 2;                       // whole 128-slice pieces
-        e->fl_ncp = ncp;
-    }
+    if (!e->fl_ncp) e->fl_ncp = plan_ncp(e, e->fl_nseg, true);      // whole 128-slice pieces
     if (!e->attr_fl) {
         HIPCHK(hipFuncSetAttribute((const void *)k_fp_list, hipFuncAttributeMaxDynamicSharedMemorySize, FL_LDS_BYTES));
         e->attr_fl = true;
     }
-    const int which = (e->aux && e->stream == e->aux) ? 1 : 0;
-    float **slot = which ? &e->fl_part_aux : &e->fl_part;
-    if (!*slot) {
-        int rc = dev_alloc(e, GEOMETRY, (void **)slot, (size_t)std::max<uint32_t>(1, e->fl_nseg) * e->fl_ncp * 64 * sizeof(float), false);
-        if (rc) return rc;
-    }
+    float **slot = fp_which(e) ? &e->fl_part_aux : &e->fl_part;
+    if (int rc = fp_scratch(e, slot, e->fl_nseg, e->fl_ncp)) return rc;
+    float *part = *slot;
     for (int c0 = 0; c0 < nchunk; c0 += e->fl_ncp) {
         const int ncp = std::min(e->fl_ncp, nchunk - c0);            // even: the slab is whole 128-slice pieces
         {
             ProfScope ps(e, TOMO_K_FP_TILE);
             dim3 grid((unsigned)(8 * ((e->fl_nitems + 7) / 8) * (ncp / 2))), block(FL_THREADS);
             hipLaunchKernelGGL(k_fp_list, grid, block, FL_LDS_BYTES, e->stream, x, e->d_fl_items, e->d_fl_orient, e->d_fl_shift, e->d_fl_ent, e->d_fl_ptr,
-                               e->d_fl_fent, e->d_fl_fptr, *slot, e->n, e->sx, e->fl_nitems, c0 / 2, ncp / 2, ncp, e->d_fl_zero);
+                               e->d_fl_fent, e->d_fl_fptr, part, e->n, e->sx, e->fl_nitems, c0 / 2, ncp / 2, ncp, e->d_fl_zero);
             LAUNCHCHK();
         }
         {
             ProfScope ps(e, TOMO_K_FP_REDUCE);
-            launch_fp_reduce<MODE>(e, e->stream, *slot, e->d_fl_rsptr, e->d_fl_rsidx, b, out, c0, ncp);
+            launch_fp_reduce<MODE>(e, e->stream, part, e->d_fl_rsptr, e->d_fl_rsidx, b, rowfac, out, c0, ncp);
             LAUNCHCHK();
         }
     }
@@ -155,26 +174,21 @@ static Forms select_forms(const tomo_engine *e)
 
 // all-angle FP: sheared-strip form, else the tile-stationary form (k_fp_tile + k_fp_tile_reduce) unless switched off, else the ray-driven form
 template <int MODE>
-static int launch_fp_all(tomo_engine *e, const float *x, const float *b, float *out)
+static int launch_fp_all(tomo_engine *e, const float *x, const float *b, float *out, const float *rowfac = nullptr)
 {
+    if (!rowfac) rowfac = e->d_rowsum;
     const int form = select_forms(e).fp;
-    if (form == TOMO_FORM_FP_LIST) return launch_fp_list<MODE>(e, x, b, out);
-    if (form == TOMO_FORM_FP_STRIP) return launch_fp_strip<MODE>(e, x, b, out);
-    if (form == TOMO_FORM_FP_ROWS) return launch_fp<MODE>(e, x, 0, (int)e->nrows, b, out, e->fp_all_lpr);
+    if (form == TOMO_FORM_FP_LIST) return launch_fp_list<MODE>(e, x, b, out, rowfac);
+    if (form == TOMO_FORM_FP_STRIP) return launch_fp_strip<MODE>(e, x, b, out, rowfac);
+    if (form == TOMO_FORM_FP_ROWS) return launch_fp<MODE>(e, x, 0, (int)e->nrows, b, out, e->fp_all_lpr, rowfac);
     const int nchunk = e->sxc / 64;
     if (!e->ft_ncp) {
-        size_t per_chunk = (size_t)std::max<uint32_t>(1, e->ft_nseg) * 64 * sizeof(float);
-        int ncp = (int)std::min<size_t>(nchunk, std::max<size_t>(1, e->ft_scratch_cap / per_chunk));
-        if (e->ft_ncp_forced > 0) ncp = std::min(nchunk, e->ft_ncp_forced);
-        else if (ncp >= 4) ncp &= ~3; else if (ncp >= 2) ncp &= ~1;
-        e->ft_ncp = ncp;
+        e->ft_ncp = plan_ncp(e, e->ft_nseg, false);
         if (!e->attr_fp) {   // per engine: the attribute belongs to the (function, device) pair
             HIPCHK(hipFuncSetAttribute((const void *)k_fp_tile, hipFuncAttributeMaxDynamicSharedMemorySize, FT_LDS_BYTES));
             e->attr_fp = true;
         }
     }
-    const int which = (e->aux && e->stream == e->aux) ? 1 : 0;
-    float **slot = which ? &e->ft_part_aux : &e->ft_part;
     // The tile kernel is LDS / vector-ALU bound and WRITES the partial sums; the reduce kernel is HBM-read bound.  With
     // "fp_tile_pipe" = P >= 2 the projection runs as P groups of chunks, the reduce of group k on a helper stream beside the tile
     // kernel of group k+1 (two halves of the scratch, events both ways): the two kernels want different parts of the chip.
@@ -188,12 +202,10 @@ static int launch_fp_all(tomo_engine *e, const float *x, const float *b, float *
         per = (per + 1) & ~1;
         if (per <= e->ft_ncp && per < nchunk) { ncp_call = per; pipe = 1; }
     }
-    if (!*slot) {
-        // sized for both schemes: one pass of ft_ncp chunks, or two halves of a pipelined group each
-        size_t chunks = std::max<size_t>(e->ft_ncp, 2 * (size_t)((((e->sxc / 64 + 1) / 2) + 1) & ~1));
-        int rc = dev_alloc(e, GEOMETRY, (void **)slot, (size_t)std::max<uint32_t>(1, e->ft_nseg) * chunks * 64 * sizeof(float), false);
-        if (rc) return rc;
-    }
+    // sized for both schemes: one pass of ft_ncp chunks, or two halves of a pipelined group each
+    const int which = fp_which(e);
+    float **slot = which ? &e->ft_part_aux : &e->ft_part;
+    if (int rc = fp_scratch(e, slot, e->ft_nseg, std::max<size_t>(e->ft_ncp, 2 * (size_t)((((e->sxc / 64 + 1) / 2) + 1) & ~1)))) return rc;
     if (pipe && !e->fp_red_stream[which]) {
         HIPCHK(hipStreamCreateWithFlags(&e->fp_red_stream[which], hipStreamNonBlocking));
         for (int h = 0; h < 2; ++h) {
@@ -222,7 +234,7 @@ static int launch_fp_all(tomo_engine *e, const float *x, const float *b, float *
         }
         {
             ProfScope ps(e, TOMO_K_FP_REDUCE, rs);
-            launch_fp_reduce<MODE>(e, rs, part, e->d_ft_rsptr, e->d_ft_rsidx, b, out, c0, ncp);
+            launch_fp_reduce<MODE>(e, rs, part, e->d_ft_rsptr, e->d_ft_rsidx, b, rowfac, out, c0, ncp);
             LAUNCHCHK();
         }
         if (pipe) HIPCHK(hipEventRecord(e->ev_fp_red[which][half], rs));
@@ -244,32 +256,28 @@ static int launch_sino_resid(tomo_engine *e, const float *b, const float *g, flo
     return TOMO_OK;
 }
 
+// A slab larger than the Infinity Cache is streamed (non-temporal tile accesses); a smaller one stays cached between the
+// launches of consecutive angles and keeps plain accesses (see st_xload / st_xstore).  "sart_nt": 0 never, 1 always, -1 by size.
+static bool slab_streams(const tomo_engine *e)
+{
+    if (e->sart_nt >= 0) return e->sart_nt != 0;
+    return (size_t)e->npix * e->sx * sizeof(float) >= ((size_t)192 << 20);
+}
+
 constexpr int BP_PPW = 4;
 
 static int launch_bp_angle(tomo_engine *e, const Sub &sb, float *x, int angle, const float *r_angle, float beta, float *track = nullptr)
 {
     ProfScope ps(e, TOMO_K_BP_ANGLE, sb.stream);
-    const int vec = sub_vec(e, sb);
-    int nchunk = e->sxc / (64 * vec), chunk0 = 0;
-    if (sb.nc) { nchunk = sb.nc / vec; chunk0 = sb.c0 / vec; }   // sub-slab (whole multiples of 64*vec slices)
-    int ngroups = (int)((e->npix + BP_PPW - 1) / BP_PPW);
-    int64_t waves = (int64_t)ngroups * nchunk;
-    dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-    const CellD *cell = e->d_cell + (size_t)angle * e->npix;
-    if (track) {   // caller brackets with reduce_begin / reduce_end
-        switch (vec) {
-        case 4: hipLaunchKernelGGL((k_bp_angle<4, BP_PPW, true>), grid, block, 0, sb.stream, x, cell, r_angle, beta, (int)e->npix, e->sx, ngroups, nchunk, track, e->d_part, chunk0); break;
-        case 2: hipLaunchKernelGGL((k_bp_angle<2, BP_PPW, true>), grid, block, 0, sb.stream, x, cell, r_angle, beta, (int)e->npix, e->sx, ngroups, nchunk, track, e->d_part, chunk0); break;
-        default: hipLaunchKernelGGL((k_bp_angle<1, BP_PPW, true>), grid, block, 0, sb.stream, x, cell, r_angle, beta, (int)e->npix, e->sx, ngroups, nchunk, track, e->d_part, chunk0); break;
-        }
-        LAUNCHCHK();
-        return TOMO_OK;
-    }
-    switch (vec) {
-    case 4: hipLaunchKernelGGL((k_bp_angle<4, BP_PPW, false>), grid, block, 0, sb.stream, x, cell, r_angle, beta, (int)e->npix, e->sx, ngroups, nchunk, (float *)nullptr, (double *)nullptr, chunk0); break;
-    case 2: hipLaunchKernelGGL((k_bp_angle<2, BP_PPW, false>), grid, block, 0, sb.stream, x, cell, r_angle, beta, (int)e->npix, e->sx, ngroups, nchunk, (float *)nullptr, (double *)nullptr, chunk0); break;
-    default: hipLaunchKernelGGL((k_bp_angle<1, BP_PPW, false>), grid, block, 0, sb.stream, x, cell, r_angle, beta, (int)e->npix, e->sx, ngroups, nchunk, (float *)nullptr, (double *)nullptr, chunk0); break;
-    }
+    const int vec = sub_vec(e, sb);              // (a sub-slab is whole multiples of 64*vec slices)
+    const Chunks ch = chunks64(e, sb);
+    const int nchunk = ch.n / vec, ngroups = (int)((e->npix + BP_PPW - 1) / BP_PPW);
+    dim3 grid((unsigned)(((int64_t)ngroups * nchunk + 3) / 4)), block(256);
+    double *part = track ? e->d_part : nullptr;  // tracked: the caller brackets with reduce_begin / reduce_end
+    with_vec(vec, [&](auto V) { with_flag(track != nullptr, [&](auto T) {
+        hipLaunchKernelGGL((k_bp_angle<V(), BP_PPW, T()>), grid, block, 0, sb.stream, x, e->d_cell + (size_t)angle * e->npix, r_angle, beta, (int)e->npix, e->sx,
+                           ngroups, nchunk, track, part, ch.c0 / vec);
+    }); });
     LAUNCHCHK();
     return TOMO_OK;
 }
@@ -277,6 +285,21 @@ static int launch_bp_angle(tomo_engine *e, const Sub &sb, float *x, int angle, c
 static int launch_bp_angle(tomo_engine *e, float *x, int angle, const float *r_angle, float beta, float *track = nullptr)
 {
     return launch_bp_angle(e, whole(e), x, angle, r_angle, beta, track);
+}
+
+// the chained ART's back projection of angle `angle` (k_bp_art); a = the rows k_art_chain left, all angles
+static int launch_bp_art(tomo_engine *e, const Sub &sb, float *x, int angle, const float *a, float beta)
+{
+    const int vec = sub_vec(e, sb);
+    const Chunks ch = chunks64(e, sb);
+    const int nchunk = ch.n / vec, ngroups = (int)((e->npix + BP_PPW - 1) / BP_PPW);
+    dim3 grid((unsigned)(((int64_t)ngroups * nchunk + 3) / 4));
+    with_vec(vec, [&](auto V) {
+        hipLaunchKernelGGL((k_bp_art<V(), BP_PPW>), grid, dim3(256), 0, sb.stream, x, e->d_cell + (size_t)angle * e->npix, a + (size_t)angle * e->n * e->sx, beta,
+                           (int)e->npix, e->sx, ngroups, nchunk, slab_streams(e) ? 1 : 0, ch.c0 / vec);
+    });
+    LAUNCHCHK();
+    return TOMO_OK;
 }
 
 // segmented per-angle step: FUSED -> BP(prev) + FP(next); else plain FP(next).  Leaves the residual rows of `next` in r.
@@ -296,20 +319,16 @@ static int launch_sart_seg(tomo_engine *e, const float *x_old, float *x_new, int
     if (L > 0) {
         ProfScope ps(e, FUSED ? TOMO_K_SART_FUSED : TOMO_K_FP_ANGLE);
         dim3 grid((unsigned)(8 * (int64_t)L * nchunk)), block(64);
-        switch (e->vec) {
-        case 4: hipLaunchKernelGGL((k_sart_seg<4, 8, FUSED>), grid, block, 0, e->stream, x_old, x_new, exec, L, e->d_went, cell, rp, beta, e->seg_partial, e->sx); break;
-        case 2: hipLaunchKernelGGL((k_sart_seg<2, 8, FUSED>), grid, block, 0, e->stream, x_old, x_new, exec, L, e->d_went, cell, rp, beta, e->seg_partial, e->sx); break;
-        default: hipLaunchKernelGGL((k_sart_seg<1, 8, FUSED>), grid, block, 0, e->stream, x_old, x_new, exec, L, e->d_went, cell, rp, beta, e->seg_partial, e->sx); break;
-        }
+        with_vec(e->vec, [&](auto V) {
+            hipLaunchKernelGGL((k_sart_seg<V(), 8, FUSED>), grid, block, 0, e->stream, x_old, x_new, exec, L, e->d_went, cell, rp, beta, e->seg_partial, e->sx);
+        });
         LAUNCHCHK();
     }
     {
         dim3 grid((unsigned)((int64_t)e->n * nchunk)), block(256);
-        switch (e->vec) {
-        case 4: hipLaunchKernelGGL((k_resid_finish<4>), grid, block, 0, e->stream, e->seg_partial, e->d_row_first, e->d_row_nseg, e->cur_b, e->d_rowsum, r, next * e->n, e->n, nchunk, e->sx, 0); break;
-        case 2: hipLaunchKernelGGL((k_resid_finish<2>), grid, block, 0, e->stream, e->seg_partial, e->d_row_first, e->d_row_nseg, e->cur_b, e->d_rowsum, r, next * e->n, e->n, nchunk, e->sx, 0); break;
-        default: hipLaunchKernelGGL((k_resid_finish<1>), grid, block, 0, e->stream, e->seg_partial, e->d_row_first, e->d_row_nseg, e->cur_b, e->d_rowsum, r, next * e->n, e->n, nchunk, e->sx, 0); break;
-        }
+        with_vec(e->vec, [&](auto V) {
+            hipLaunchKernelGGL((k_resid_finish<V()>), grid, block, 0, e->stream, e->seg_partial, e->d_row_first, e->d_row_nseg, e->cur_b, e->d_rowsum, r, next * e->n, e->n, nchunk, e->sx, 0);
+        });
         LAUNCHCHK();
     }
     return TOMO_OK;
@@ -347,35 +366,17 @@ static int sart_tile_prepare(tomo_engine *e, bool coop)
     return TOMO_OK;
 }
 
-// A slab larger than the Infinity Cache is streamed (non-temporal tile accesses); a smaller one stays cached between the
-// launches of consecutive angles and keeps plain accesses (see st_xload / st_xstore).  "sart_nt": 0 never, 1 always, -1 by size.
-static bool slab_streams(const tomo_engine *e)
-{
-    if (e->sart_nt >= 0) return e->sart_nt != 0;
-    return (size_t)e->npix * e->sx * sizeof(float) >= ((size_t)192 << 20);
-}
-
 // residual rows of angle `next` from the tile partial sums in `partial` (k_resid_finish)
 static int launch_resid_finish_tile(tomo_engine *e, const Sub &sb, const float *partial, int next, float *r, bool sum = false)
 {
-    const int nchunk64 = sb.nc ? sb.nc : e->sxc / 64, c64 = sb.nc ? sb.c0 : 0;
-    const int vec = sub_vec(e, sb);
-    int nchunk = nchunk64 / vec, chunk0 = c64 / vec;
+    const Chunks ch = chunks64(e, sb);
+    const int vec = sub_vec(e, sb), nchunk = ch.n / vec;
     dim3 grid((unsigned)((int64_t)e->n * nchunk)), block(256);
-    if (sum) {      // plain row sums (chained ART: k_art_chain forms the residuals)
-        switch (vec) {
-        case 4: hipLaunchKernelGGL((k_resid_finish<4, true>), grid, block, 0, sb.stream, partial, e->d_st_row_first, e->d_st_row_nseg, e->cur_b, e->d_rowsum, r, next * e->n, e->n, nchunk, e->sx, chunk0); break;
-        case 2: hipLaunchKernelGGL((k_resid_finish<2, true>), grid, block, 0, sb.stream, partial, e->d_st_row_first, e->d_st_row_nseg, e->cur_b, e->d_rowsum, r, next * e->n, e->n, nchunk, e->sx, chunk0); break;
-        default: hipLaunchKernelGGL((k_resid_finish<1, true>), grid, block, 0, sb.stream, partial, e->d_st_row_first, e->d_st_row_nseg, e->cur_b, e->d_rowsum, r, next * e->n, e->n, nchunk, e->sx, chunk0); break;
-        }
-        LAUNCHCHK();
-        return TOMO_OK;
-    }
-    switch (vec) {
-    case 4: hipLaunchKernelGGL((k_resid_finish<4>), grid, block, 0, sb.stream, partial, e->d_st_row_first, e->d_st_row_nseg, e->cur_b, e->d_rowsum, r, next * e->n, e->n, nchunk, e->sx, chunk0); break;
-    case 2: hipLaunchKernelGGL((k_resid_finish<2>), grid, block, 0, sb.stream, partial, e->d_st_row_first, e->d_st_row_nseg, e->cur_b, e->d_rowsum, r, next * e->n, e->n, nchunk, e->sx, chunk0); break;
-    default: hipLaunchKernelGGL((k_resid_finish<1>), grid, block, 0, sb.stream, partial, e->d_st_row_first, e->d_st_row_nseg, e->cur_b, e->d_rowsum, r, next * e->n, e->n, nchunk, e->sx, chunk0); break;
-    }
+    // sum: plain row sums (chained ART: k_art_chain forms the residuals)
+    with_vec(vec, [&](auto V) { with_flag(sum, [&](auto S) {
+        hipLaunchKernelGGL((k_resid_finish<V(), S()>), grid, block, 0, sb.stream, partial, e->d_st_row_first, e->d_st_row_nseg, e->cur_b, e->d_rowsum, r, next * e->n, e->n,
+                           nchunk, e->sx, ch.c0 / vec);
+    }); });
     LAUNCHCHK();
     return TOMO_OK;
 }
@@ -387,20 +388,19 @@ template <bool FUSED, bool ART = false>
 static int launch_sart_tile(tomo_engine *e, const Sub &sb, float *x, int prev, int next, float *r, float beta,
                             float *partial = nullptr, bool finish = true, int64_t key = -1, float *fp_out = nullptr)
 {
-    const int nchunk64 = sb.nc ? sb.nc : e->sxc / 64, c64 = sb.nc ? sb.c0 : 0;
+    const Chunks ch = chunks64(e, sb);
     const size_t nt = (size_t)e->st_ntiles;
     if (!partial) partial = e->st_partial;
     {
         ProfScope ps(e, FUSED ? TOMO_K_SART_FUSED : TOMO_K_FP_ANGLE, sb.stream, key);
-        dim3 grid((unsigned)(8 * ((e->st_ntiles + 7) / 8) * nchunk64)), block(ST_THREADS);
-        auto go = [&](auto kern) {
-            hipLaunchKernelGGL(kern, grid, block, ST_LDS_V * 16, sb.stream, x, x,
+        dim3 grid((unsigned)(8 * ((e->st_ntiles + 7) / 8) * ch.n)), block(ST_THREADS);
+        with_flag(slab_streams(e), [&](auto NT) {
+            hipLaunchKernelGGL((k_sart_tile<FUSED, false, NT(), ART && FUSED>), grid, block, ST_LDS_V * 16, sb.stream, x, x,
                                FUSED ? e->d_st_cell + (size_t)prev * nt * ST_PIX : nullptr, FUSED ? e->d_st_win + (size_t)prev * nt : nullptr,
                                FUSED ? r + (size_t)prev * e->n * e->sx : nullptr, beta,
                                e->d_st_seg + (size_t)next * nt * ST_MAXSEG, e->d_st_segid + (size_t)next * nt * ST_MAXSEG, e->d_st_ent, partial,
-                               e->n, e->sx, e->st_tiles_z, e->st_ntiles, nchunk64, c64, e->sart_skip_same, StCoop{});
-        };
-        if (slab_streams(e)) go(k_sart_tile<FUSED, false, true, ART && FUSED>); else go(k_sart_tile<FUSED, false, false, ART && FUSED>);
+                               e->n, e->sx, e->st_tiles_z, e->st_ntiles, ch.n, ch.c0, e->sart_skip_same, StCoop{});
+        });
         LAUNCHCHK();
     }
     if (ART) return launch_resid_finish_tile(e, sb, partial, next, fp_out, true);
@@ -411,10 +411,10 @@ static int launch_sart_tile(tomo_engine *e, const Sub &sb, float *x, int prev, i
 static int launch_sart_coop(tomo_engine *e, const Sub &sb, float *x, int prev, int next, float *r, float beta,
                             const float *p_read, float *p_write, uint32_t epoch, int64_t key = -1)
 {
-    const int nchunk64 = sb.nc ? sb.nc : e->sxc / 64, c64 = sb.nc ? sb.c0 : 0;
+    const Chunks ch = chunks64(e, sb);
     const size_t nt = (size_t)e->st_ntiles;
     ProfScope ps(e, TOMO_K_SART_FUSED, sb.stream, key);
-    const unsigned nblocks = (unsigned)(8 * ((e->st_ntiles + 7) / 8) * nchunk64);
+    const unsigned nblocks = (unsigned)(8 * ((e->st_ntiles + 7) / 8) * ch.n);
     StCoop co;
     co.p_read = p_read;
     co.row_first = e->d_st_row_first + (size_t)prev * e->n;
@@ -424,17 +424,16 @@ static int launch_sart_coop(tomo_engine *e, const Sub &sb, float *x, int prev, i
     co.r_out = r + (size_t)prev * e->n * e->sx;
     co.flags = e->st_flags;
     co.epoch = epoch;
-    co.nitems = e->n * nchunk64;
+    co.nitems = e->n * ch.n;
     co.nred = (int)std::min<unsigned>(nblocks, (unsigned)std::max(1, e->st_resident));
     co.nchunk_all = e->sxc / 64;
     co.spin = e->sart_coop_spin;
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(nblocks), dim3(ST_THREADS), ST_LDS_V * 16, sb.stream, x, x,
+    with_flag(slab_streams(e), [&](auto NT) {
+        hipLaunchKernelGGL((k_sart_tile<true, true, NT()>), dim3(nblocks), dim3(ST_THREADS), ST_LDS_V * 16, sb.stream, x, x,
                            e->d_st_cell + (size_t)prev * nt * ST_PIX, e->d_st_win + (size_t)prev * nt, r + (size_t)prev * e->n * e->sx, beta,
                            e->d_st_seg + (size_t)next * nt * ST_MAXSEG, e->d_st_segid + (size_t)next * nt * ST_MAXSEG, e->d_st_ent, p_write,
-                           e->n, e->sx, e->st_tiles_z, e->st_ntiles, nchunk64, c64, e->sart_skip_same, co);
-    };
-    if (slab_streams(e)) go(k_sart_tile<true, true, true>); else go(k_sart_tile<true, true, false>);
+                           e->n, e->sx, e->st_tiles_z, e->st_ntiles, ch.n, ch.c0, e->sart_skip_same, co);
+    });
     LAUNCHCHK();
     return TOMO_OK;
 }
@@ -472,11 +471,9 @@ static int launch_bp_all(tomo_engine *e, float *x, const float *r, const float *
     int ngroups = (int)((e->npix + BP_PPW - 1) / BP_PPW);
     int64_t waves = (int64_t)ngroups * nchunk;
     dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-    switch (e->vec) {
-    case 4: hipLaunchKernelGGL((k_bp_all<4, BP_PPW>), grid, block, 0, e->stream, x, e->d_cell, r, colsum, alpha, beta, clamp, e->np, e->n, (int)e->npix, e->sx, ngroups, nchunk); break;
-    case 2: hipLaunchKernelGGL((k_bp_all<2, BP_PPW>), grid, block, 0, e->stream, x, e->d_cell, r, colsum, alpha, beta, clamp, e->np, e->n, (int)e->npix, e->sx, ngroups, nchunk); break;
-    default: hipLaunchKernelGGL((k_bp_all<1, BP_PPW>), grid, block, 0, e->stream, x, e->d_cell, r, colsum, alpha, beta, clamp, e->np, e->n, (int)e->npix, e->sx, ngroups, nchunk); break;
-    }
+    with_vec(e->vec, [&](auto V) {
+        hipLaunchKernelGGL((k_bp_all<V(), BP_PPW>), grid, block, 0, e->stream, x, e->d_cell, r, colsum, alpha, beta, clamp, e->np, e->n, (int)e->npix, e->sx, ngroups, nchunk);
+    });
     LAUNCHCHK();
     return TOMO_OK;
 }

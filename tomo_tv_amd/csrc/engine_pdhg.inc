@@ -21,8 +21,9 @@ static void pdhg_scalar_steps(const tomo_engine *e, float ratio, float *sigma, f
 static int pdhg_sino_launch(tomo_engine *e, float *q, const float *g, const float *b, float sigma, int precond)
 {
     const int64_t n4 = (int64_t)e->sino_elems() / 4;
-    if (precond) hipLaunchKernelGGL(k_pdhg_sino<true>, dim3(grid_1d(n4)), dim3(256), 0, e->stream, (f4 *)q, (const f4 *)g, (const f4 *)b, e->d_rowsum, sigma, n4, e->sx / 4);
-    else hipLaunchKernelGGL(k_pdhg_sino<false>, dim3(grid_1d(n4)), dim3(256), 0, e->stream, (f4 *)q, (const f4 *)g, (const f4 *)b, e->d_rowsum, sigma, n4, e->sx / 4);
+    with_flag(precond != 0, [&](auto PRE) {
+        hipLaunchKernelGGL(k_pdhg_sino<PRE()>, dim3(grid_1d(n4)), dim3(256), 0, e->stream, (f4 *)q, (const f4 *)g, (const f4 *)b, e->d_rowsum, sigma, n4, e->sx / 4);
+    });
     LAUNCHCHK();
     return TOMO_OK;
 }
@@ -53,10 +54,9 @@ static int pdhg_tv_launch(tomo_engine *e, float *x, float **xbar, const float *u
     dim3 grid(tv_march_grid(e->n, PD_TZ, e->sxc / 64, (e->n + yseg - 1) / yseg));
     {
         ProfScope ps(e, TOMO_K_PDHG_TV);
-#define PDHG_GO(PRE, SUM) hipLaunchKernelGGL((k_pdhg_tv<PRE, SUM>), grid, dim3(256), 0, e->stream, A, e->d_part, e->n, e->nx, e->sx, yseg)
-        if (precond) { if (slot >= 0) PDHG_GO(true, true); else PDHG_GO(true, false); }
-        else { if (slot >= 0) PDHG_GO(false, true); else PDHG_GO(false, false); }
-#undef PDHG_GO
+        with_flag(precond != 0, [&](auto PRE) { with_flag(slot >= 0, [&](auto SUM) {
+            hipLaunchKernelGGL((k_pdhg_tv<PRE(), SUM()>), grid, dim3(256), 0, e->stream, A, e->d_part, e->n, e->nx, e->sx, yseg);
+        }); });
     }
     LAUNCHCHK();
     std::swap(*xbar, e->pdhg_alt[0]);

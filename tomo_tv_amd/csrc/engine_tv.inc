@@ -167,40 +167,37 @@ static int tv_grad_impl(tomo_engine *e, float eps, bool with_tv, float *g_first 
     {
         ProfScope ps(e, TOMO_K_TV_GRAD);
         e->tv_last_eps = eps;
+        double *part_tv = with_tv ? e->d_part_tv : nullptr;
         if (e->tv_lds == 1 && e->tv_recompute) {   // sum g^2 (and TV) only: the update pass re-evaluates g (TVM_UPDATE)
             TvUpd gp{};
             gp.wrap_lo = g_last; gp.wrap_hi = g_first;      // g's last / first slice (slab-sharded descent), or null
-            const int yseg = tv_rows_per_wave(e, e->tv_tz == 4 ? 4 : 8);
-            if (e->tv_tz == 4) {
-                dim3 grid(tv_march_grid(e->n, 4, e->sxc / 64, (e->n + yseg - 1) / yseg));
-                if (with_tv) hipLaunchKernelGGL((k_tv_grad_reg<4, true, true, TVM_NORM>), grid, dim3(256), 0, e->stream, x, h, (float *)nullptr, e->d_part, eps, e->n, e->nx, e->sx, yseg, e->d_part_tv, gp);
-                else hipLaunchKernelGGL((k_tv_grad_reg<4, false, true, TVM_NORM>), grid, dim3(256), 0, e->stream, x, h, (float *)nullptr, e->d_part, eps, e->n, e->nx, e->sx, yseg, (double *)nullptr, gp);
-            } else {
-            dim3 grid(tv_march_grid(e->n, 8, e->sxc / 64, (e->n + yseg - 1) / yseg));
-            if (e->tv_march4) {
-                const bool edge = e->nx % 64 != 0 || e->n % 8 != 0;      // lanes without a voxel exist: the predicated form
-#define TV4_NORM(WTV, EDGE, PTV) hipLaunchKernelGGL((k_tv_march4<8, WTV, TVM_NORM, EDGE>), grid, dim3(256), 0, e->stream, x, h, e->d_part, eps, e->n, e->nx, e->sx, yseg, PTV, gp)
-                if (with_tv) { if (edge) TV4_NORM(true, true, e->d_part_tv); else TV4_NORM(true, false, e->d_part_tv); }
-                else { if (edge) TV4_NORM(false, true, (double *)nullptr); else TV4_NORM(false, false, (double *)nullptr); }
-#undef TV4_NORM
-            }
-            else if (with_tv) hipLaunchKernelGGL((k_tv_grad_reg<8, true, true, TVM_NORM>), grid, dim3(256), 0, e->stream, x, h, (float *)nullptr, e->d_part, eps, e->n, e->nx, e->sx, yseg, e->d_part_tv, gp);
-            else hipLaunchKernelGGL((k_tv_grad_reg<8, false, true, TVM_NORM>), grid, dim3(256), 0, e->stream, x, h, (float *)nullptr, e->d_part, eps, e->n, e->nx, e->sx, yseg, (double *)nullptr, gp);
-            }
+            const int tz = e->tv_tz == 4 ? 4 : 8, yseg = tv_rows_per_wave(e, tz);
+            dim3 grid(tv_march_grid(e->n, tz, e->sxc / 64, (e->n + yseg - 1) / yseg));
+            const bool edge = e->nx % 64 != 0 || e->n % 8 != 0;      // lanes without a voxel exist: the march's predicated form
+            with_flag(with_tv, [&](auto W) {
+                if (tz == 8 && e->tv_march4) with_flag(edge, [&](auto E) {
+                    hipLaunchKernelGGL((k_tv_march4<8, W(), TVM_NORM, E()>), grid, dim3(256), 0, e->stream, x, h, e->d_part, eps, e->n, e->nx, e->sx, yseg, part_tv, gp);
+                });
+                else with_int<4, 8>(tz, [&](auto TZ) {
+                    hipLaunchKernelGGL((k_tv_grad_reg<TZ(), W(), true, TVM_NORM>), grid, dim3(256), 0, e->stream, x, h, (float *)nullptr, e->d_part, eps, e->n, e->nx, e->sx, yseg, part_tv, gp);
+                });
+            });
         } else if (e->tv_lds == 1) {   // register march (k_tv_grad_reg): one wave per (z block, chunk, y segment)
             int yseg = 32;   // 8 .. 64 rows per wave measured the same; longer segments leave too few waves
             dim3 grid(tv_march_grid(e->n, 8, e->sxc / 64, (e->n + yseg - 1) / yseg));
-            if (with_tv) hipLaunchKernelGGL((k_tv_grad_reg<8, true>), grid, dim3(256), 0, e->stream, x, h, g, e->d_part, eps, e->n, e->nx, e->sx, yseg, e->d_part_tv, TvUpd{});
-            else hipLaunchKernelGGL((k_tv_grad_reg<8, false>), grid, dim3(256), 0, e->stream, x, h, g, e->d_part, eps, e->n, e->nx, e->sx, yseg, (double *)nullptr, TvUpd{});
+            with_flag(with_tv, [&](auto W) {
+                hipLaunchKernelGGL((k_tv_grad_reg<8, W()>), grid, dim3(256), 0, e->stream, x, h, g, e->d_part, eps, e->n, e->nx, e->sx, yseg, part_tv, TvUpd{});
+            });
         } else if (e->tv_lds) {
             int yseg = 32;
-            if (e->tv_lds == 16) {
+            if (e->tv_lds == 16) {      // (no folded value: with_tv is off)
                 dim3 grid((unsigned)(((e->n + 15) / 16) * (e->sxc / 64)), (unsigned)((e->n + yseg - 1) / yseg));
                 hipLaunchKernelGGL((k_tv_grad_lds<16, false>), grid, dim3(256), 0, e->stream, x, h, g, e->d_part, eps, e->n, e->nx, e->sx, yseg, (double *)nullptr);
             } else {
                 dim3 grid((unsigned)(((e->n + 7) / 8) * (e->sxc / 64)), (unsigned)((e->n + yseg - 1) / yseg));
-                if (with_tv) hipLaunchKernelGGL((k_tv_grad_lds<8, true>), grid, dim3(256), 0, e->stream, x, h, g, e->d_part, eps, e->n, e->nx, e->sx, yseg, e->d_part_tv);
-                else hipLaunchKernelGGL((k_tv_grad_lds<8, false>), grid, dim3(256), 0, e->stream, x, h, g, e->d_part, eps, e->n, e->nx, e->sx, yseg, (double *)nullptr);
+                with_flag(with_tv, [&](auto W) {
+                    hipLaunchKernelGGL((k_tv_grad_lds<8, W()>), grid, dim3(256), 0, e->stream, x, h, g, e->d_part, eps, e->n, e->nx, e->sx, yseg, part_tv);
+                });
             }
         } else {
             hipLaunchKernelGGL(k_tv_grad, dim3(tv_grid(e)), dim3(256), 0, e->stream, x, h, g, e->d_part, eps, e->n, e->nx, e->sx);
@@ -252,6 +249,20 @@ int tomo_tv_halo_apply(tomo_engine *e, float dPOCS, int clamp, const void *g_lo,
     return TOMO_OK;
 }
 
+// the engine's pair of halo planes that is NOT in use (the second pair is allocated on first use): what a pass that still reads the
+// planes in use writes the next ones into
+static int halo_other_pair(tomo_engine *e, float **lo, float **hi)
+{
+    int rc;
+    if (!e->halo_lo_alt) {
+        if ((rc = dev_alloc(e, ENGINE, (void **)&e->halo_lo_alt, e->npix * sizeof(float), true))) return rc;
+        if ((rc = dev_alloc(e, ENGINE, (void **)&e->halo_hi_alt, e->npix * sizeof(float), true))) return rc;
+    }
+    *lo = e->halo_lo == e->halo_lo_own ? e->halo_lo_alt : e->halo_lo_own;
+    *hi = e->halo_hi == e->halo_hi_own ? e->halo_hi_alt : e->halo_hi_own;
+    return TOMO_OK;
+}
+
 // wrap: also write the new last / first slice into the engine's halo planes (single slab, periodic); plane_last /
 // plane_first: into caller buffers instead (slab-sharded: the planes the ring exchange sends next)
 // hg_lo / hg_hi (slab-sharded descent): the gradient planes received from the ring neighbours; the halo planes are advanced with them
@@ -281,43 +292,25 @@ static int tv_update_impl(tomo_engine *e, float dPOCS, int clamp, int track_vol,
         if ((rc = get_scratch(e, &e->tv_alt, &alt))) return rc;
         const bool own_halo = e->halo_lo == e->halo_lo_own || e->halo_lo == e->halo_lo_alt;
         float *wl = plane_last, *wh = plane_first;
-        if (wrap && own_halo) {
-            if (!e->halo_lo_alt) {
-                if ((rc = dev_alloc(e, ENGINE, (void **)&e->halo_lo_alt, e->npix * sizeof(float), true))) return rc;
-                if ((rc = dev_alloc(e, ENGINE, (void **)&e->halo_hi_alt, e->npix * sizeof(float), true))) return rc;
-            }
-            wl = e->halo_lo == e->halo_lo_own ? e->halo_lo_alt : e->halo_lo_own;
-            wh = e->halo_hi == e->halo_hi_own ? e->halo_hi_alt : e->halo_hi_own;
-        }
+        if (wrap && own_halo && (rc = halo_other_pair(e, &wl, &wh))) return rc;
         Halo h{e->halo_lo, e->halo_hi};
         TvUpd up{alt, gnorm_ptr(e), dPOCS, clamp, track, wl, wh, slab_streams(e) ? 1 : 0, nullptr, nullptr, nullptr, nullptr};
         const bool fold = hg_lo && hg_hi && (e->tv_halo_fold < 0 ? e->sxc >= 128 : e->tv_halo_fold != 0) && own_halo && !wrap && e->tv_tz != 4 && e->tv_march4;
         if (fold) {
-            if (!e->halo_lo_alt) {
-                if ((rc = dev_alloc(e, ENGINE, (void **)&e->halo_lo_alt, e->npix * sizeof(float), true))) return rc;
-                if ((rc = dev_alloc(e, ENGINE, (void **)&e->halo_hi_alt, e->npix * sizeof(float), true))) return rc;
-            }
             up.hg_lo = hg_lo; up.hg_hi = hg_hi;
-            up.ho_lo = e->halo_lo == e->halo_lo_own ? e->halo_lo_alt : e->halo_lo_own;
-            up.ho_hi = e->halo_hi == e->halo_hi_own ? e->halo_hi_alt : e->halo_hi_own;
+            if ((rc = halo_other_pair(e, &up.ho_lo, &up.ho_hi))) return rc;
         }
         {
             ProfScope ps(e, TOMO_K_TV_UPDATE);
-            const int yseg = tv_rows_per_wave(e, e->tv_tz == 4 ? 4 : 8);
-            if (e->tv_tz == 4) {
-                dim3 grid(tv_march_grid(e->n, 4, e->sxc / 64, (e->n + yseg - 1) / yseg));
-                hipLaunchKernelGGL((k_tv_grad_reg<4, false, true, TVM_UPDATE>), grid, dim3(256), 0, e->stream, x, h, (float *)nullptr, e->d_part, e->tv_last_eps, e->n, e->nx, e->sx, yseg, (double *)nullptr, up);
-            } else {
-            dim3 grid(tv_march_grid(e->n, 8, e->sxc / 64, (e->n + yseg - 1) / yseg));
-            if (e->tv_march4) {
-                const bool edge = e->nx % 64 != 0 || e->n % 8 != 0, trk = track != nullptr, strm = up.stream != 0;
-#define TV4_UPD(EDGE, TRK, STRM) hipLaunchKernelGGL((k_tv_march4<8, false, TVM_UPDATE, EDGE, TRK, STRM>), grid, dim3(256), 0, e->stream, x, h, e->d_part, e->tv_last_eps, e->n, e->nx, e->sx, yseg, (double *)nullptr, up)
-                if (edge) { if (trk) { if (strm) TV4_UPD(true, true, true); else TV4_UPD(true, true, false); } else { if (strm) TV4_UPD(true, false, true); else TV4_UPD(true, false, false); } }
-                else { if (trk) { if (strm) TV4_UPD(false, true, true); else TV4_UPD(false, true, false); } else { if (strm) TV4_UPD(false, false, true); else TV4_UPD(false, false, false); } }
-#undef TV4_UPD
-            }
-            else hipLaunchKernelGGL((k_tv_grad_reg<8, false, true, TVM_UPDATE>), grid, dim3(256), 0, e->stream, x, h, (float *)nullptr, e->d_part, e->tv_last_eps, e->n, e->nx, e->sx, yseg, (double *)nullptr, up);
-            }
+            const int tz = e->tv_tz == 4 ? 4 : 8, yseg = tv_rows_per_wave(e, tz);
+            dim3 grid(tv_march_grid(e->n, tz, e->sxc / 64, (e->n + yseg - 1) / yseg));
+            const bool edge = e->nx % 64 != 0 || e->n % 8 != 0;
+            if (tz == 8 && e->tv_march4) with_flag(edge, [&](auto E) { with_flag(track != nullptr, [&](auto T) { with_flag(up.stream != 0, [&](auto S) {
+                hipLaunchKernelGGL((k_tv_march4<8, false, TVM_UPDATE, E(), T(), S()>), grid, dim3(256), 0, e->stream, x, h, e->d_part, e->tv_last_eps, e->n, e->nx, e->sx, yseg, (double *)nullptr, up);
+            }); }); });
+            else with_int<4, 8>(tz, [&](auto TZ) {
+                hipLaunchKernelGGL((k_tv_grad_reg<TZ(), false, true, TVM_UPDATE>), grid, dim3(256), 0, e->stream, x, h, (float *)nullptr, e->d_part, e->tv_last_eps, e->n, e->nx, e->sx, yseg, (double *)nullptr, up);
+            });
         }
         LAUNCHCHK();
         e->vol[e->tv_target] = alt; e->tv_alt = x;              // the updated volume lives in the partner buffer
@@ -331,8 +324,10 @@ static int tv_update_impl(tomo_engine *e, float dPOCS, int clamp, int track_vol,
     {
         ProfScope ps(e, TOMO_K_TV_UPDATE);
         float *wl = wrap ? e->halo_lo : plane_last, *wh = wrap ? e->halo_hi : plane_first;
-        if (track) hipLaunchKernelGGL(k_tv_update<true>, dim3(grid_1d(n4)), dim3(256), 0, e->stream, (f4 *)x, (const f4 *)g, gnorm_ptr(e), dPOCS, clamp, n4, (f4 *)track, e->d_part, wl, wh, e->nx, e->sx / 4);
-        else hipLaunchKernelGGL(k_tv_update<false>, dim3(grid_1d(n4)), dim3(256), 0, e->stream, (f4 *)x, (const f4 *)g, gnorm_ptr(e), dPOCS, clamp, n4, (f4 *)nullptr, (double *)nullptr, wl, wh, e->nx, e->sx / 4);
+        double *part = track ? e->d_part : nullptr;
+        with_flag(track != nullptr, [&](auto T) {
+            hipLaunchKernelGGL(k_tv_update<T()>, dim3(grid_1d(n4)), dim3(256), 0, e->stream, (f4 *)x, (const f4 *)g, gnorm_ptr(e), dPOCS, clamp, n4, (f4 *)track, part, wl, wh, e->nx, e->sx / 4);
+        });
     }
     LAUNCHCHK();
     if (hg_lo && hg_hi && (rc = tomo_tv_halo_apply(e, dPOCS, clamp, hg_lo, hg_hi))) return rc;
@@ -504,12 +499,10 @@ int tomo_fgp_fused_step(tomo_engine *e, float lambda, int first_iteration)
     if (fgp_sharded(e)) { ed.p1_lo = e->fgp_lo; ed.hi = e->fgp_hi; ed.send_first = e->fgp_send_first; ed.send_last = e->fgp_send_last; }
     {
         ProfScope ps(e, TOMO_K_FGP_GRAD);
-        if (fgp_sharded(e))
-            hipLaunchKernelGGL(k_fgp_fused<true>, grid, dim3(256), 0, e->stream, e->vol[e->fgp_target], e->fgp_p[0], e->fgp_p[1], e->fgp_p[2],
+        with_flag(fgp_sharded(e), [&](auto SH) {
+            hipLaunchKernelGGL(k_fgp_fused<SH()>, grid, dim3(256), 0, e->stream, e->vol[e->fgp_target], e->fgp_p[0], e->fgp_p[1], e->fgp_p[2],
                                e->fgp_q[0], e->fgp_q[1], e->fgp_q[2], lambda, multip, e->n, e->nx, e->sx, yseg, first_iteration ? 1 : 0, ed);
-        else
-            hipLaunchKernelGGL(k_fgp_fused<false>, grid, dim3(256), 0, e->stream, e->vol[e->fgp_target], e->fgp_p[0], e->fgp_p[1], e->fgp_p[2],
-                               e->fgp_q[0], e->fgp_q[1], e->fgp_q[2], lambda, multip, e->n, e->nx, e->sx, yseg, first_iteration ? 1 : 0, ed);
+        });
     }
     LAUNCHCHK();
     for (int k = 0; k < 3; ++k) std::swap(e->fgp_p[k], e->fgp_q[k]);
@@ -530,13 +523,11 @@ int tomo_fgp_fused_step2(tomo_engine *e, float lambda, int first_iteration)
     const float multip = 1.0f / (26.0f * lambda);
     {
         ProfScope ps(e, TOMO_K_FGP_GRAD);
-        if (fgp_sharded(e)) {
-            Fgp2Edge ed{e->fgp_lo, e->fgp_hi, e->fgp_send_first, e->fgp_send_last, e->is_first, e->is_last};
-            hipLaunchKernelGGL((k_fgp_fused2<false, true>), grid, dim3(256), 0, e->stream, e->vol[e->fgp_target], e->fgp_p[0], e->fgp_p[1], e->fgp_p[2],
+        const Fgp2Edge ed = fgp_sharded(e) ? Fgp2Edge{e->fgp_lo, e->fgp_hi, e->fgp_send_first, e->fgp_send_last, e->is_first, e->is_last} : Fgp2Edge{};
+        with_flag(fgp_sharded(e), [&](auto SH) {
+            hipLaunchKernelGGL((k_fgp_fused2<false, SH()>), grid, dim3(256), 0, e->stream, e->vol[e->fgp_target], e->fgp_p[0], e->fgp_p[1], e->fgp_p[2],
                                e->fgp_q[0], e->fgp_q[1], e->fgp_q[2], lambda, multip, e->n, e->nx, e->sx, yseg, first_iteration ? 1 : 0, ed);
-        } else
-        hipLaunchKernelGGL((k_fgp_fused2<false, false>), grid, dim3(256), 0, e->stream, e->vol[e->fgp_target], e->fgp_p[0], e->fgp_p[1], e->fgp_p[2],
-                           e->fgp_q[0], e->fgp_q[1], e->fgp_q[2], lambda, multip, e->n, e->nx, e->sx, yseg, first_iteration ? 1 : 0, Fgp2Edge{});
+        });
     }
     LAUNCHCHK();
     for (int k = 0; k < 3; ++k) std::swap(e->fgp_p[k], e->fgp_q[k]);
