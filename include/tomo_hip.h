@@ -252,7 +252,8 @@ int tomo_tv_fgp_vol(tomo_engine *e, int vol, int iters, float lambda);  /* multi
  * Pock-Chambolle 2011, alpha = 1): S_i = 1 / rowsum_i (0 for an empty ray), s_grad = 1/2, T_j = 1 / (colsum_j + d_j), d_j = the
  * difference rows that touch voxel j (0..6); sigma and tau are not read.
  * All four calls run on the engine's stream and never synchronise; they return TOMO_ERR_STATE on an engine with a communicator or
- * whose slab is not both first and last (tomo_set_slab_edges): the slab-sharded form needs halo planes of p and xbar. */
+ * whose slab is not both first and last (tomo_set_slab_edges): a slab of a sharded volume has the tomo_pdhg_slab_* / tomo_comm_pdhg*
+ * calls below, which read the neighbours' p and xbar from halo planes. */
 /* step 1 on sinogram slots (q may be TOMO_SINO_USER0 + k); tv_chambolle.cu has no data term: the dual sinogram is new here */
 int tomo_pdhg_sino_dual(tomo_engine *e, int q_sino, int g_sino, int b_sino, float sigma, int precond);
 /* step 3 as ONE fused pass over caller-named volume slots (counterpart of the dual / primal kernels sketched in tv_chambolle.cu):
@@ -266,6 +267,35 @@ int tomo_pdhg_tv_step(tomo_engine *e, int x_vol, int xbar_vol, int u_vol, int p_
  * slot: as above, of the last iteration. */
 int tomo_pdhg_begin(tomo_engine *e);
 int tomo_pdhg(tomo_engine *e, int niter, float lambda, float theta, int precond, float ratio, int slot);
+/* ---- the same on a slab of a volume sharded along the tilt axis --------------------------------------------------------------
+ * Only the fused pass couples slices (grad along s, div along s); the projections and the dual sinogram are slice-local.  The
+ * neighbours' slices reach it through caller-owned device planes of Nray*Nray floats, dense [y][z] (the reference's sharded engine
+ * exchanges whole boundary slices the same way: cpu/utils/mpi_ctvlib.cpp:400-422):
+ *     lo          4 planes [xbar, p0, p1, p2] of the slice below this slab        hi         1 plane, xbar of the slice above
+ *     send_last   4 planes [xbar, p0, p1, p2] of this slab's last slice           send_first 1 plane, xbar of its slice 0
+ * The caller moves send_last -> next.lo and send_first -> prev.hi before each step: 5 N^2 floats per rank and iteration, one round.
+ * The pass itself leaves the new boundary fields in the send planes (no pack launch per iteration); a neighbour's dual step is
+ * re-evaluated from its planes with the same float32 operations, so the sharded result has the bits of the whole-volume pass.
+ * A face flagged as the volume's end (tomo_set_slab_edges) reads and writes no plane.  An engine with a communicator that has bound
+ * nothing gets planes of its own.  mpi_ctvlib.cpp:400-422 is the ring these replace. */
+int tomo_bind_pdhg_halo(tomo_engine *e, void *lo, void *hi, void *send_first, void *send_last);
+/* both send buffers from named volume slots (before the first step, or after a start from fields the pass did not write);
+ * the boundary slices mpi_ctvlib.cpp:400-422 sends */
+int tomo_pdhg_slab_pack(tomo_engine *e, int xbar_vol, int p_vol0);
+/* tomo_pdhg_tv_step on a slab: same arguments and checks; honours the slab edges, reads lo / hi as they are (mpi_ctvlib.cpp:400-422
+ * fills them), leaves the new boundary fields in the send buffers; `slot` receives THIS slab's partial sum.  A slab that is both first
+ * and last needs no planes and gives the bits of tomo_pdhg_tv_step; TOMO_ERR_STATE where planes are needed and none are bound. */
+int tomo_pdhg_slab_tv_step(tomo_engine *e, int x_vol, int xbar_vol, int u_vol, int p_vol0, float sigma, float tau, float lambda,
+                           float theta, int precond, int slot);
+/* tomo_pdhg_sino_dual on a slab (slice-local: no plane, no exchange) */
+int tomo_pdhg_slab_sino_dual(tomo_engine *e, int q_sino, int g_sino, int b_sino, float sigma, int precond);
+/* the state of tomo_pdhg_begin (p = 0, q = 0, xbar = RECON) plus the send buffers packed from it (mpi_ctvlib.cpp:400-422) */
+int tomo_pdhg_slab_begin(tomo_engine *e);
+/* ONE iteration of tomo_pdhg without the exchange, which the caller runs before it (mpi_ctvlib.cpp:400-422): forward projection of
+ * xbar, dual sinogram, back projection, the fused slab pass.  Arguments as tomo_pdhg's; TOMO_ERR_STATE before tomo_pdhg_slab_begin.
+ * The scalar step sizes come from the engine's L_A (tomo_lipschitz), which depends on the 2-D matrix only: every rank derives the
+ * same sigma and tau without an all-reduce. */
+int tomo_pdhg_slab_iter(tomo_engine *e, float lambda, float theta, int precond, float ratio, int slot);
 
 /* ---- multimodal (ChemicalTomo) element-wise steps ---------------------------------------------------------
  * Two engines with the same slab shape on one device and stream: `ce` carries the chemical geometry and the
@@ -401,6 +431,13 @@ int tomo_comm_tv_gd(tomo_engine *e, int ng, float dPOCS, float eps, int track_vo
 int tomo_comm_fgp_exchange(tomo_engine *e);
 /* ... and before a PAIR of them (tomo_fgp_fused_step2 on slabs): the two-slice-deep planes of tomo_bind_fgp_halo2, one round per two iterations */
 int tomo_comm_fgp_exchange2(tomo_engine *e);
+/* the plane exchange before an iteration of the slab-sharded Chambolle-Pock loop (buffers of tomo_bind_pdhg_halo, or the engine's
+ * own): ONE group, 1 plane towards prev and 4 towards next -- the ring of mpi_ctvlib.cpp:400-422 */
+int tomo_comm_pdhg_exchange(tomo_engine *e);
+/* slab-sharded tomo_pdhg, whole call: niter x {that exchange, tomo_pdhg_slab_iter} on the engine's stream (mpi_ctvlib.cpp:400-422 per
+ * iteration); `slot` keeps this slab's partial sum of the last iteration.  TOMO_ERR_STATE without a communicator or before
+ * tomo_pdhg_slab_begin. */
+int tomo_comm_pdhg(tomo_engine *e, int niter, float lambda, float theta, int precond, float ratio, int slot);
 
 /* launch chains a SART / ART sweep of this engine's slab runs as under the current "sart_streams" (1 = one chain on the
  * engine's stream; 2..4 = that many sub-slabs of 64-slice chunks on their own streams).  What the reference hides inside

@@ -124,6 +124,12 @@ SIGNATURES = {
     "tomo_pdhg_tv_step": [_p, _i, _i, _i, _i, _f, _f, _f, _f, _i, _i],
     "tomo_pdhg_begin": [_p],
     "tomo_pdhg": [_p, _i, _f, _f, _i, _f, _i],
+    "tomo_bind_pdhg_halo": [_p, _p, _p, _p, _p],
+    "tomo_pdhg_slab_pack": [_p, _i, _i],
+    "tomo_pdhg_slab_tv_step": [_p, _i, _i, _i, _i, _f, _f, _f, _f, _i, _i],
+    "tomo_pdhg_slab_sino_dual": [_p, _i, _i, _i, _f, _i],
+    "tomo_pdhg_slab_begin": [_p],
+    "tomo_pdhg_slab_iter": [_p, _f, _f, _i, _f, _i],
     "tomo_get_stream": [_p, _pp],
     "tomo_mm_model": [_p, _p, _i, _p, _f, _p, _i],
     "tomo_mm_update": [_p, _p, _p, _i, _p, _f, _f, _f, _p, _i, _i],
@@ -139,6 +145,8 @@ SIGNATURES = {
     "tomo_comm_tv_gd": [_p, _i, _f, _f, _i, _i],
     "tomo_comm_fgp_exchange": [_p],
     "tomo_comm_fgp_exchange2": [_p],
+    "tomo_comm_pdhg_exchange": [_p],
+    "tomo_comm_pdhg": [_p, _i, _f, _f, _i, _f, _i],
     "tomo_profile_enable": [_p, _i, _i],
     "tomo_profile_read": [_p, _i, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)],
     "tomo_profile_read2": [_p, _i, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)],

@@ -66,6 +66,7 @@ static void comm_release(tomo_engine *e)
     }
     e->comm = nullptr;
     if (e->comm_fgp && e->fgp_lo == e->comm_fgp) { e->fgp_lo = e->fgp_hi = e->fgp_send_first = e->fgp_send_last = nullptr; e->fgp_planes2 = false; }
+    if (e->comm_pdhg && e->pdhg_lo == e->comm_pdhg) e->pdhg_lo = e->pdhg_hi = e->pdhg_send_first = e->pdhg_send_last = nullptr;
     e->pool.release_life(COMM);
 }
 
@@ -79,6 +80,10 @@ static int comm_buffers(tomo_engine *e)
         if ((rc = dev_alloc(e, COMM, (void **)&e->comm_fgp, 26 * e->npix * sizeof(float), true))) return rc;
         e->fgp_lo = e->comm_fgp; e->fgp_hi = e->comm_fgp + 5 * e->npix; e->fgp_send_first = e->comm_fgp + 13 * e->npix; e->fgp_send_last = e->comm_fgp + 21 * e->npix;
         e->fgp_planes2 = true;
+    }
+    if (!e->pdhg_lo) {       // ... and the planes of the Chambolle-Pock pass (tomo_bind_pdhg_halo): lo 4, hi 1, send_first 1, send_last 4
+        if ((rc = dev_alloc(e, COMM, (void **)&e->comm_pdhg, 10 * e->npix * sizeof(float), true))) return rc;
+        e->pdhg_lo = e->comm_pdhg; e->pdhg_hi = e->comm_pdhg + 4 * e->npix; e->pdhg_send_first = e->comm_pdhg + 5 * e->npix; e->pdhg_send_last = e->comm_pdhg + 6 * e->npix;
     }
     return dev_alloc(e, COMM, (void **)&e->comm_scal, TOMO_S_COUNT * sizeof(double), true);
 }
@@ -275,4 +280,20 @@ int tomo_comm_fgp_exchange2(tomo_engine *e)
     NEED_COMM(e);
     if (!e->fgp_lo || !e->fgp_planes2) return fail(TOMO_ERR_STATE, "the two-deep FGP exchange needs the two-slice-deep planes (tomo_bind_fgp_halo2)");
     return comm_group(e, "fgp exchange (two deep)", [&] { return comm_ring(e, e->fgp_send_first, 8 * (size_t)e->npix, e->fgp_send_last, 5 * (size_t)e->npix, e->fgp_lo, e->fgp_hi); });
+}
+
+// the exchange before an iteration of the slab-sharded Chambolle-Pock loop: send_last (xbar, p0, p1, p2 of my last slice) -> next's
+// lo, send_first (xbar of my first slice) -> prev's hi (tomo_bind_pdhg_halo names the four buffers): 5 N^2 floats per rank, one round
+int tomo_comm_pdhg_exchange(tomo_engine *e)
+{
+    NEED_COMM(e);
+    if (!e->pdhg_lo) return fail(TOMO_ERR_STATE, "slab-sharded pdhg_tv needs its planes (tomo_bind_pdhg_halo)");
+    return comm_group(e, "pdhg exchange", [&] { return comm_ring(e, e->pdhg_send_first, (size_t)e->npix, e->pdhg_send_last, 4 * (size_t)e->npix, e->pdhg_lo, e->pdhg_hi); });
+}
+
+// slab-sharded pdhg_tv, whole call: niter x {exchange, iteration}, every launch and every group on the engine's stream
+int tomo_comm_pdhg(tomo_engine *e, int niter, float lambda, float theta, int precond, float ratio, int slot)
+{
+    NEED_COMM(e);
+    return pdhg_loop(e, niter, lambda, theta, precond, ratio, slot, [&] { return tomo_comm_pdhg_exchange(e); });
 }

@@ -35,6 +35,26 @@ __device__ __forceinline__ void pdhg_dual(float c, float cs, float cy, float cz,
     o0 = __fmul_rn(a0, inv); o1 = __fmul_rn(a1, inv); o2 = __fmul_rn(a2, inv);
 }
 
+// SLAB: the planes of a slab of a sharded volume, dense [y][z] (n * n floats each).  The slice below the slab (lo = xbar, p0, p1, p2)
+// and xbar of the slice above (hi) stand in for the neighbours' slices; the pass leaves what the neighbours need next in send_first
+// (xbar_new of slice 0) and send_last (xbar_new, p0_new, p1_new, p2_new of slice nx - 1).  first / last: the slab holds the volume's end.
+struct PdhgSlab {
+    const float *lo, *hi;
+    float *send_first, *send_last;
+    int first, last;
+};
+
+// the same, left as a and 1 / max(1, |a|_2 / lambda): p_new = a * inv
+__device__ __forceinline__ void pdhg_dual_parts(float c, float cs, float cy, float cz, float p0, float p1, float p2, bool ms, bool my, bool mz,
+                                                float sigma, float lambda, float &a0, float &a1, float &a2, float &inv)
+{
+    a0 = ms ? __fmaf_rn(sigma, __fsub_rn(cs, c), p0) : 0.f;
+    a1 = my ? __fmaf_rn(sigma, __fsub_rn(cy, c), p1) : 0.f;
+    a2 = mz ? __fmaf_rn(sigma, __fsub_rn(cz, c), p2) : 0.f;
+    const float nn = __fmaf_rn(a2, a2, __fmaf_rn(a1, a1, __fmul_rn(a0, a0)));
+    inv = __fdiv_rn(1.f, fmaxf(1.f, __fdiv_rn(__fsqrt_rn(nn), lambda)));
+}
+
 // ---- the fused pass: dual step, divergence, primal step, extrapolation ----------------------------------------------------------
 // The barrier-free register march of k_tv_grad_reg: one wave = PD_TZ z-columns x 64 slices (lane = slice), rows marched along y.
 //   slice neighbours   DPP wave shifts inside the chunk; beyond its edges the values are gathered once per row into packed registers
@@ -44,8 +64,12 @@ __device__ __forceinline__ void pdhg_dual(float c, float cs, float cy, float cz,
 //   z - 1              p_new_z of the previous column stays in a register; column z0 - 1 is evaluated again by this wave
 // Traffic per voxel: x, xbar, p0..p2, u read and x, xbar, p0..p2 written once = 44 B (the re-read halo columns and rows hit in L2).
 // SUM: also sum (x_new - x)^2 into the partial-sum buffer.  PRECOND: T = 1 / (colsum + d), d = the difference rows that touch the voxel.
-template <bool PRECOND, bool SUM>
-__global__ __launch_bounds__(256) void k_pdhg_tv(PdhgArgs A, double *__restrict__ part, int n, int nx, int sx, int yseg)
+// SLAB: a slab face that is not the volume's end is a chunk edge whose neighbour slice lies in a plane: chunk 0 evaluates p_new_s of the
+//   slice below from the lo planes (the packed evaluation, same bits as the neighbour's own), and xbar of the slice above reaches the
+//   lane of slice nx - 1 through lane 63's packed register (nx % 64 == 0) or stands in for the padding slice nx in that lane's upper
+//   neighbour (a partial chunk: that lane stores 0 like every padding lane).  d counts the difference rows of the global volume.
+template <bool PRECOND, bool SUM, bool SLAB>
+__global__ __launch_bounds__(256) void k_pdhg_tv(PdhgArgs A, double *__restrict__ part, int n, int nx, int sx, int yseg, PdhgSlab E)
 {
     constexpr int TZ = PD_TZ;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -65,7 +89,12 @@ __global__ __launch_bounds__(256) void k_pdhg_tv(PdhgArgs A, double *__restrict_
         const int y0 = ys * yseg, y1 = min(y0 + yseg, n);
         const int z0 = bz * TZ, s0 = bs * 64, s = s0 + lane;
         const bool has_lo = s0 > 0, has_hi = s0 + 64 < nx;          // wave-uniform: the chunk has a neighbour below / above
-        const bool valid = s < nx, ms = s < nx - 1;
+        const bool valid = s < nx, ms = s < nx - 1 || (SLAB && s == nx - 1 && !E.last);
+        const bool lo_pl = SLAB && s0 == 0 && !E.first;            // wave-uniform: slice s0 - 1 is the lo planes
+        const bool hi_pl = SLAB && !has_hi && !E.last;             // wave-uniform: slice nx is the hi plane ...
+        const bool hi_edge = hi_pl && s0 + 64 == nx, hi_mid = hi_pl && s0 + 64 > nx;   // ... beyond lane 63, or at the lane of slice nx
+        const bool below = s > 0 || (SLAB && !E.first), above = s < nx - 1 || (SLAB && !E.last);   // the difference rows along s exist
+        const int npix = n * n;
         int zc[TZ + 2];                                             // columns z0 - 1 .. z0 + TZ, clamped into the image (masks decide what counts)
 #pragma unroll
         for (int j = 0; j < TZ + 2; ++j) zc[j] = min(max(z0 - 1 + j, 0), n - 1);
@@ -85,11 +114,22 @@ __global__ __launch_bounds__(256) void k_pdhg_tv(PdhgArgs A, double *__restrict_
 #pragma unroll
         for (int j = 0; j < TZ + 2; ++j) c0[j] = A.xbar[(size_t)(ystart * n + zc[j]) * sx + (unsigned)s];
         float PE0 = has_lo ? A.xbar[(size_t)(ystart * n + zl) * sx + (unsigned)(s0 - 1)] : 0.f;   // xbar at slice s0 - 1, packed
+        if (SLAB && lo_pl) PE0 = E.lo[ystart * n + zl];
+        if (SLAB && hi_mid) {
+            const float h = E.hi[ystart * n + zl];
+#pragma unroll
+            for (int j = 0; j < TZ + 2; ++j) c0[j] = s == nx ? lanev(h, j) : c0[j];
+        }
         for (int y = ystart; y < y1; ++y) {
             const bool emit = y >= y0, my = y < n - 1;
             const int yn = min(y + 1, n - 1);
 #pragma unroll
             for (int j = 0; j < TZ + 2; ++j) cp[j] = A.xbar[(size_t)(yn * n + zc[j]) * sx + (unsigned)s];
+            if (SLAB && hi_mid) {
+                const float h = E.hi[yn * n + zl];
+#pragma unroll
+                for (int j = 0; j < TZ + 2; ++j) cp[j] = s == nx ? lanev(h, j) : cp[j];
+            }
             const size_t pl = (size_t)(y * n + zl) * sx;
             // p_new_s at slice s0 - 1 of this row, all columns at once
             float PEp = 0.f, phs = 0.f;
@@ -100,8 +140,16 @@ __global__ __launch_bounds__(256) void k_pdhg_tv(PdhgArgs A, double *__restrict_
                 float o1, o2;
                 pdhg_dual(PE0, pc, PEp, kz, A.p0[pl + (unsigned)(s0 - 1)], A.p1[pl + (unsigned)(s0 - 1)], A.p2[pl + (unsigned)(s0 - 1)],
                           true, my, mzl, A.sigma, A.lambda, phs, o1, o2);
+            } else if (SLAB && lo_pl) {
+                const int at = y * n + zl;
+                PEp = E.lo[yn * n + zl];
+                const float pc = A.xbar[pl];
+                const float kz = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, PE0), 0x101, 0xf, 0xf, false));
+                float o1, o2;
+                pdhg_dual(PE0, pc, PEp, kz, E.lo[npix + at], E.lo[2 * npix + at], E.lo[3 * npix + at], true, my, mzl, A.sigma, A.lambda, phs, o1, o2);
             }
-            const float PH = has_hi ? A.xbar[pl + (unsigned)(s0 + 64)] : 0.f;      // xbar at slice s0 + 64, packed
+            float PH = has_hi ? A.xbar[pl + (unsigned)(s0 + 64)] : 0.f;            // xbar at slice s0 + 64, packed
+            if (SLAB && hi_edge) PH = E.hi[y * n + zl];
             float pzp = 0.f;                                        // p_new_z of column z - 1 (column -1: 0)
 #pragma unroll
             for (int j = 0; j <= TZ; ++j) {
@@ -109,15 +157,34 @@ __global__ __launch_bounds__(256) void k_pdhg_tv(PdhgArgs A, double *__restrict_
                 if (z < 0 || z >= n) continue;                      // wave-uniform
                 const size_t at = (size_t)(y * n + z) * sx + (unsigned)s;
                 const float cs = shl(lanev(PH, j), c0[j]);
-                float n0, n1, n2;
-                pdhg_dual(c0[j], cs, cp[j], c0[j + 1], A.p0[at], A.p1[at], A.p2[at], ms, my, z < n - 1, A.sigma, A.lambda, n0, n1, n2);
+                float n0, n1, n2, b0 = 0.f, b1 = 0.f, b2 = 0.f, binv = 0.f;
+                if (SLAB) {
+                    pdhg_dual_parts(c0[j], cs, cp[j], c0[j + 1], A.p0[at], A.p1[at], A.p2[at], ms, my, z < n - 1, A.sigma, A.lambda, b0, b1, b2, binv);
+                    n0 = __fmul_rn(b0, binv); n1 = __fmul_rn(b1, binv); n2 = __fmul_rn(b2, binv);
+                    asm volatile("" : "+v"(n0), "+v"(n1), "+v"(n2));       // the rounded products: nothing below may fuse them again
+                } else {
+                    pdhg_dual(c0[j], cs, cp[j], c0[j + 1], A.p0[at], A.p1[at], A.p2[at], ms, my, z < n - 1, A.sigma, A.lambda, n0, n1, n2);
+                }
                 if (j >= 1) {
                     if (emit) {
                         const float psm = shr(lanev(phs, j), n0);  // p_new_s at slice s - 1 (slice -1: 0, phs is 0 without a chunk below)
-                        const float dv = __fadd_rn(__fadd_rn(__fsub_rn(n0, s > 0 ? psm : 0.f), __fsub_rn(n1, pyp[j])), __fsub_rn(n2, pzp));
+                        float dv;
+                        if (SLAB) {
+                            // The divergence of the whole-volume form, operation for operation.  The *_rn helpers are plain operators to
+                            // the compiler, and in the SLAB = false code it fuses the product a * inv into the subtraction of the s term
+                            // (and of the z term in the wave's last column, whose p_new_z no next column needs), so x_new sees
+                            // unrounded products there.  A sharded run must give those bits (tests/test_gpu_pdhg_sharded.py holds the
+                            // two forms together): spelled out here.
+                            const float t0 = __fmaf_rn(b0, binv, -(below ? psm : 0.f));
+                            const float t1 = n1 - pyp[j];
+                            const float t2 = j == TZ ? __fmaf_rn(b2, binv, -pzp) : n2 - pzp;
+                            dv = (t0 + t1) + t2;
+                        } else {
+                            dv = __fadd_rn(__fadd_rn(__fsub_rn(n0, below ? psm : 0.f), __fsub_rn(n1, pyp[j])), __fsub_rn(n2, pzp));
+                        }
                         float T = A.tau;
                         if (PRECOND) {
-                            const int d = (s > 0) + (s < nx - 1) + (y > 0) + (y < n - 1) + (z > 0) + (z < n - 1);
+                            const int d = below + above + (y > 0) + (y < n - 1) + (z > 0) + (z < n - 1);
                             const float den = __fadd_rn(A.colsum[y * n + z], (float)d);
                             T = den > 0.f ? __fdiv_rn(1.f, den) : 0.f;
                         }
@@ -126,10 +193,18 @@ __global__ __launch_bounds__(256) void k_pdhg_tv(PdhgArgs A, double *__restrict_
                         const float dx = __fsub_rn(xn, xo);
                         if (SUM && valid) acc += (double)__fmul_rn(dx, dx);
                         A.x[at] = valid ? xn : 0.f;
-                        A.xbar_out[at] = valid ? __fmaf_rn(A.theta, dx, xn) : 0.f;
+                        const float xb = __fmaf_rn(A.theta, dx, xn);
+                        A.xbar_out[at] = valid ? xb : 0.f;
                         A.q0[at] = valid ? n0 : 0.f;
                         A.q1[at] = valid ? n1 : 0.f;
                         A.q2[at] = valid ? n2 : 0.f;
+                        if (SLAB) {
+                            const int pa = y * n + z;
+                            if (s == 0 && !E.first) E.send_first[pa] = xb;
+                            if (s == nx - 1 && !E.last) {
+                                E.send_last[pa] = xb; E.send_last[npix + pa] = n0; E.send_last[2 * npix + pa] = n1; E.send_last[3 * npix + pa] = n2;
+                            }
+                        }
                     }
                     pyp[j] = n1;
                 }

@@ -287,6 +287,8 @@ struct tomo_engine {
     // fused pass (xbar, p0..p2), which change places with the buffers of the fields it wrote
     float *pdhg_p[3] = {nullptr, nullptr, nullptr}, *pdhg_alt[4] = {nullptr, nullptr, nullptr, nullptr}, *pdhg_q = nullptr;
     bool pdhg_begun = false;
+    // planes of the slab-sharded fused pass (caller-owned device buffers, tomo_bind_pdhg_halo): lo 4, hi 1, send_first 1, send_last 4
+    float *pdhg_lo = nullptr, *pdhg_hi = nullptr, *pdhg_send_first = nullptr, *pdhg_send_last = nullptr;
     float *stage = nullptr;
     size_t stage_bytes = 0;
     // scalars
@@ -302,6 +304,7 @@ struct tomo_engine {
     int64_t comm_rounds = 0;                      // RCCL rounds (one ncclGroup or one lone collective) this engine has enqueued: bench.py's rccl_rounds_per_step
     float *comm_send_first = nullptr, *comm_send_last = nullptr, *comm_g_lo = nullptr, *comm_g_hi = nullptr;   // N*N planes
     float *comm_fgp = nullptr;                    // the engine's own planes of the fused FGP exchange when the host binds none
+    float *comm_pdhg = nullptr;                   // ... and of the slab-sharded Chambolle-Pock pass (10 planes)
     double *comm_scal = nullptr;                  // TOMO_S_COUNT doubles: the all-reduced copy of the scalar buffer
     // "the model sinogram G is A * (volume v in its present state)": set by a plain projection into G (tomo_forward_projection,
     // tomo_data_distance_sq), inherited by a copy of v, dropped by anything else that touches G or writes v (fp_reuse, below)
@@ -328,7 +331,7 @@ struct tomo_engine {
     size_t vol_elems() const { return (size_t)npix * sx; }
     size_t sino_elems() const { return (size_t)nrows * sx; }
     // every device allocation of the engine (dev_pool.h).  Caller-bound buffers and the aliases of owned ones (d_scal, halo_lo / halo_hi,
-    // fgp_lo ..., gnorm_override) are never registered.
+    // fgp_lo ..., pdhg_lo ..., gnorm_override) are never registered.
     DevPool pool{pool_alloc, pool_free};
 };
 

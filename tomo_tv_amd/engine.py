@@ -97,6 +97,11 @@ class _SlabBackend:
         self.c("bind_halo", ctypes.c_void_p(self._halo_lo.data_ptr()), ctypes.c_void_p(self._halo_hi.data_ptr()))
         self.c("bind_fgp_halo2", *(ctypes.c_void_p(t.data_ptr()) for t in
                                    (self._fgp_lo, self._fgp_hi, self._fgp_send_first, self._fgp_send_last)))
+        # planes of the slab-sharded Chambolle-Pock pass (tomo_bind_pdhg_halo): lo = [xbar, p0, p1, p2](-1), hi = xbar(nx), and what
+        # this slab sends: xbar of its slice 0, [xbar, p0, p1, p2] of its last slice
+        self._pdhg_lo, self._pdhg_hi, self._pdhg_send_first, self._pdhg_send_last = z(4), z(1), z(1), z(4)
+        self.c("bind_pdhg_halo", *(ctypes.c_void_p(t.data_ptr()) for t in
+                                   (self._pdhg_lo, self._pdhg_hi, self._pdhg_send_first, self._pdhg_send_last)))
 
     def enable_native_comm(self, comm):
         """A native RCCL communicator for this engine (include/tomo_hip.h: tomo_comm_*): rank 0 makes the id, the process
@@ -180,6 +185,10 @@ class _SlabBackend:
             return self._fgp_send_first, self._fgp_send_last, self._fgp_lo, self._fgp_hi
         npix = self.nray * self.nray
         return self._fgp_send_first[:4 * npix], self._fgp_send_last[:npix], self._fgp_lo[:npix], self._fgp_hi[:4 * npix]
+
+    def pdhg_planes(self):
+        """(send_first, send_last, lo, hi) of the slab-sharded Chambolle-Pock pass: 1 / 4 / 4 / 1 planes."""
+        return self._pdhg_send_first, self._pdhg_send_last, self._pdhg_lo, self._pdhg_hi
 
     def new_plane(self):
         import torch
@@ -860,32 +869,62 @@ class _EngineBase:
 
     # ---- Chambolle-Pock (include/tomo_hip.h: tomo_pdhg*) -----------------------------------------------------------------------
     def _pdhg_one_engine(self):
-        """The iteration couples neighbouring slices through p and xbar; the slab-sharded form (halo planes of both) does not exist."""
-        if self.comm is not None or self.sub_slabs > 1 or not isinstance(self.be, _SlabBackend):
+        """One engine per rank: the whole volume, or a slab of it with a ``comm`` (the halo planes of p and xbar travel round the ring).
+        Sub-slabs on one GPU are a launch-overlap device of the SART sweep, not sharding."""
+        if self.sub_slabs > 1 or not isinstance(self.be, _SlabBackend):
             raise NotImplementedError("pdhg_tv runs on one whole-volume engine")
+
+    def pdhg_planes(self):
+        """(send_first, send_last, lo, hi) of the slab-sharded pass (device tensors of 1 / 4 / 4 / 1 planes); sharded engines only."""
+        return self.be.pdhg_planes()
+
+    def pdhg_slab_pack(self, xbar_vol, p_vol0):
+        """Sharded step form: this slab's boundary slices of xbar and p into the send planes (before the first ``pdhg_exchange``)."""
+        self.be.c("pdhg_slab_pack", int(xbar_vol), int(p_vol0))
+
+    def pdhg_exchange(self):
+        """Sharded: send_last -> next rank's lo, send_first -> previous rank's hi; one round, before every step or iteration."""
+        if self._native():
+            self.be.c("comm_pdhg_exchange")
+        else:
+            first, last, lo, hi = self.be.pdhg_planes()
+            self.comm.exchange_planes(first, last, lo, hi)
 
     def pdhg_begin(self):
         """p = 0, q = 0, xbar = recon: the state ``pdhg`` iterates on, kept until the next begin."""
         self._pdhg_one_engine()
-        self.be.c("pdhg_begin")
+        self.be.c("pdhg_begin" if self.comm is None else "pdhg_slab_begin")
 
     def pdhg(self, niter, lam, theta=1.0, precond=True, ratio=1.0, slot=-1):
         """``niter`` Chambolle-Pock iterations of min_{x >= 0} 1/2 |Ax - b|^2 + lam |grad x|_{2,1} on recon (after ``pdhg_begin``).
         ``precond``: diagonal step sizes (no Lipschitz estimate, no tuning); False: scalar tau = ratio / sqrt(L_A + 12),
-        sigma = 1 / (ratio sqrt(L_A + 12)).  ``slot``: scalar slot that receives sum (x_new - x)^2 of the last iteration."""
+        sigma = 1 / (ratio sqrt(L_A + 12)).  ``slot``: scalar slot that receives sum (x_new - x)^2 of the last iteration.
+        Sharded: one ring exchange of 5 planes before every iteration; the same bits on every partition of the slices that runs the
+        same projector forms."""
         self._pdhg_one_engine()
-        self.be.c("pdhg", int(niter), float(lam), float(theta), int(bool(precond)), float(ratio), int(slot))
+        niter, args = int(niter), (float(lam), float(theta), int(bool(precond)), float(ratio))
+        if self.comm is None:
+            self.be.c("pdhg", niter, *args, int(slot))
+        elif self._native():
+            self.be.c("comm_pdhg", niter, *args, int(slot))
+        else:
+            for it in range(niter):
+                self.pdhg_exchange()
+                self.be.c("pdhg_slab_iter", *args, int(slot) if it == niter - 1 else -1)
 
     def pdhg_sino_dual(self, q_sino, g_sino, b_sino, sigma=0.0, precond=True):
-        """Step form: q <- (q + S (g - b)) / (1 + S) on sinogram slots."""
+        """Step form: q <- (q + S (g - b)) / (1 + S) on sinogram slots (slice-local)."""
         self._pdhg_one_engine()
-        self.be.c("pdhg_sino_dual", int(q_sino), int(g_sino), int(b_sino), float(sigma), int(bool(precond)))
+        self.be.c("pdhg_sino_dual" if self.comm is None else "pdhg_slab_sino_dual", int(q_sino), int(g_sino), int(b_sino), float(sigma),
+                  int(bool(precond)))
 
     def pdhg_tv_step(self, x_vol, xbar_vol, u_vol, p_vol0, sigma=0.0, tau=0.0, lam=0.1, theta=1.0, precond=True, slot=-1):
-        """Step form: the fused dual / divergence / primal / extrapolation pass on volume slots (p in p_vol0 .. p_vol0 + 2)."""
+        """Step form: the fused dual / divergence / primal / extrapolation pass on volume slots (p in p_vol0 .. p_vol0 + 2).  Sharded:
+        the slab step, which reads the halo planes as they are (``pdhg_slab_pack`` once, ``pdhg_exchange`` before every step) and
+        leaves the new boundary fields in the send planes."""
         self._pdhg_one_engine()
-        self.be.c("pdhg_tv_step", int(x_vol), int(xbar_vol), int(u_vol), int(p_vol0), float(sigma), float(tau), float(lam), float(theta),
-                  int(bool(precond)), int(slot))
+        self.be.c("pdhg_tv_step" if self.comm is None else "pdhg_slab_tv_step", int(x_vol), int(xbar_vol), int(u_vol), int(p_vol0),
+                  float(sigma), float(tau), float(lam), float(theta), int(bool(precond)), int(slot))
 
     def synchronize(self):
         self.be.c("synchronize")

@@ -159,11 +159,13 @@ class TomoGPU:
                     t.fista_project_yk()                      # the cost's A r gives the next step's A yk by linearity
         return self.cost
 
+    @_on_rank_threads
     def pdhg_tv(self, Niter=100, lambda_param=0.1, theta=1.0, precond=True, ratio=1.0, show_convergence=True):
         """Chambolle-Pock (primal-dual hybrid gradient) for min_{x >= 0} 1/2 |Ax - b|^2 + lambda |grad x|_{2,1}: no inner loop, one
         forward projection, one back projection and one fused stencil pass per iteration.  ``precond=True`` (default) uses the
         diagonal step sizes of Pock and Chambolle (2011), which need no Lipschitz estimate; ``precond=False`` the scalar ones,
-        tau sigma (L_A + 12) = 1, with ``ratio`` moving weight from sigma to tau.  One whole-volume engine only.
+        tau sigma (L_A + 12) = 1, with ``ratio`` moving weight from sigma to tau.  Runs on one whole-volume engine or on a volume
+        sharded over ranks or devices (one ring exchange of 5 planes per iteration); not on ``sub_slabs``.
 
         With ``show_convergence`` the cost is ``0.5 * data_distance()**2 + lambda_param * tv()`` exactly as ``fista`` reports it.
         ``tv()`` is the periodic, eps-smoothed value while the iteration minimises the Neumann one (no wrap-around, no eps);

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Time a Chambolle-Pock iteration (tomo_pdhg) and its fused pass (k_pdhg_tv) beside the FISTA iteration and k_fgp_fused2 of the
-same session; optionally list the cost per iteration of PDHG (both step modes) and FISTA on one phantom.
+same session; optionally list the cost per iteration of PDHG (both step modes) and FISTA on one phantom.  ``--slabs K``: the fused SLAB
+pass and one whole iteration on K slab engines of one device instead (the sharded form without a second GPU).
 
 One engine, seeded phantom as tools/run_config.py.  Whole iterations: the host clock around K enqueued iterations closed by a
 synchronise (one call enqueues all K; warm-up first; the median of --reps repeats).  Kernels: the engine's HIP-event launch log
@@ -62,7 +63,71 @@ ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--lam", type=float, default=0.1)
 ap.add_argument("--converge", type=int, default=0, help="also list the cost of this many iterations of PDHG (both modes) and FISTA")
 ap.add_argument("--out", default="")
+ap.add_argument("--slabs", type=int, default=0, help="K >= 2: time the fused SLAB pass and one whole iteration on K slab engines of this device instead")
 a = ap.parse_args()
+
+
+def run_slabs(a):
+    """The volume as K slab engines on ONE device and one stream (the ring of tests/local_ring.py without the threads): per slab engine
+    the fused slab pass (k_pdhg_tv<.., SLAB>, from the launch log) and, on the host clock, one whole iteration of all K engines
+    {plane exchange by device copies, forward projection, dual sinogram, back projection, slab pass}."""
+    from tomo_tv_amd.distributed import slab_partition
+    K = a.slabs
+    ang = np.deg2rad(tilt_angles(a.nproj))
+    x = ellipsoids(a.nslice, a.n)
+    eng = []
+    for r in range(K):
+        first, cnt = slab_partition(a.nslice, K, r)
+        t = tomoengine(cnt, a.n, ang)
+        t.be.enable_torch()                                                    # binds the plane tensors, runs on torch's stream
+        t.be.c("set_slab_edges", int(r == 0), int(r == K - 1))
+        t.set_volume(x[first:first + cnt], VOL_ORIGINAL)
+        t.create_projections()
+        eng.append(t)
+
+    def exchange():
+        for r, t in enumerate(eng):
+            first, last, _, _ = t.be.pdhg_planes()
+            eng[(r + 1) % K].be.pdhg_planes()[2].copy_(last)
+            eng[(r - 1) % K].be.pdhg_planes()[3].copy_(first)
+
+    def iterate(k, precond):
+        for _ in range(k):
+            exchange()
+            for t in eng:
+                t.be.c("pdhg_slab_iter", float(a.lam), 1.0, int(precond), 1.0, -1)
+
+    def sync():
+        for t in eng:
+            t.synchronize()
+    res = dict(shape=[a.nslice, a.n, a.n], nproj=a.nproj, iters=a.iters, reps=a.reps, slabs=K, slab_slices=[t.nloc for t in eng])
+    for precond in (True, False):
+        for t in eng:
+            t.restart_recon()
+            t.be.c("pdhg_slab_begin")
+        iterate(3, precond)
+        out = []
+        for _ in range(a.reps):
+            sync()
+            t0 = time.perf_counter()
+            iterate(a.iters, precond)
+            sync()
+            out.append((time.perf_counter() - t0) * 1e3 / a.iters)
+        per = []
+        for t in eng:
+            n, kms = kernel_ms(t, K_PDHG_TV, lambda: iterate(a.iters, precond))
+            per.append(kms / max(n, 1) * 1e3)
+        res["pdhg_precond%d" % precond] = dict(ms_per_iteration_all_slabs=float(np.median(out)), k_pdhg_tv_slab_us=per)
+        print(f"pdhg slabs={K} precond={int(precond)}: {np.median(out):.3f} ms per iteration of all {K} slab engines (one stream); slab pass "
+              + " / ".join(f"{u:.1f}" for u in per) + " us per slab engine")
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if a.slabs >= 2:
+    run_slabs(a)
+    sys.exit(0)
 
 t = tomoengine(a.nslice, a.n, np.deg2rad(tilt_angles(a.nproj)))
 t.set_volume(ellipsoids(a.nslice, a.n), VOL_ORIGINAL)
