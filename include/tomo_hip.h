@@ -366,8 +366,6 @@ int tomo_mm_update(tomo_engine *ce, const int32_t *xvols, const int32_t *uvols, 
  *                     the VGPR index mode) when the engine built them ("fp_list_ready": where the strips are built and a tile's
  *                     work spreads evenly enough over the waves; TOMO_FP_LIST = 0 / 1 overrides) and the slab is a whole number
  *                     of 128-slice pieces; 0 = k_fp_strip
- *   "fp_tile_pipe" (0): experimental, P >= 2: the tile projector runs as P groups of 64-slice chunks, the reduce pass of one
- *                     group on a second stream beside the tile pass of the next (no gain measured)
  *   "sart_resident" (-1): the SART sweep as ONE launch of the volume-resident kernel (k_sart_resident: a 64-slice chunk of the whole
  *                     image stays in vector registers over all angles, the workgroups exchange ray sums).  -1 = automatic: wherever
  *                     the tables exist ("sart_resident_ready": N a multiple of 8, at most one 32 x 32 tile per CU, ray windows that

@@ -1142,6 +1142,46 @@ def test_strip_and_list_forward_projection_in_chunk_passes(gpu, monkeypatch, for
     assert rel_l2(pc, pa) < 1e-6
 
 
+@pytest.mark.parametrize("form", ["tile", "strip", "list"])
+def test_each_lane_projects_through_its_own_scratch(gpu, monkeypatch, form):
+    """Two all-angle projections of one engine in flight at once -- the data distance of TEMP on the second stream
+    (data_distance_begin) and a Landweber step on the main stream, which does not order itself behind it -- each in three
+    passes over its lane's own partial-sum scratch: sinograms and volume equal, bit for bit, those of the same two calls made
+    one after the other, in every partial-sum family."""
+    from tomo_tv_amd import _lib
+    if form == "tile":                                       # the default at this size
+        monkeypatch.delenv("TOMO_FP_STRIP", raising=False)
+        monkeypatch.delenv("TOMO_FP_LIST", raising=False)
+    else:
+        monkeypatch.setenv("TOMO_FP_STRIP", "1")
+        monkeypatch.setenv("TOMO_FP_LIST", "1" if form == "list" else "0")
+    N, P, Nx = 48, 7, 384                                    # six chunks: whole 128-slice pieces, as the list form needs
+    ang = np.linspace(-70, 65, P) * np.pi / 180
+    x = ellipsoids(Nx, N, seed=6)
+    a, b = tomoengine(Nx, N, ang), tomoengine(Nx, N, ang)
+    for t in (a, b):
+        assert _lib.FORM_FP[t.get_option("form_fp")] == form
+        t.set_option("fp_tile_chunks_per_pass", 2)
+        t.set_volume(x, VOL_ORIGINAL)
+        t.create_projections()
+        t.SIRT(1)
+        t.copy_recon()
+    a.be.c("data_distance_sq", VOL_TEMP)
+    a.be.c("sirt_landweber", VOL_RECON, 0.01, 1)
+    b.data_distance_begin(VOL_TEMP)
+    b.be.c("sirt_landweber", VOL_RECON, 0.01, 1)
+    b.data_distance_end()
+    for t in (a, b):
+        assert _lib.FORM_FP[t.get_option("form_fp")] == form
+    dd_a, dd_b = a._scalar(_lib.S_DD), b._scalar(_lib.S_DD)
+    assert dd_a > 0 and abs(dd_a - dd_b) <= 1e-12 * dd_a
+    for s in (_lib.SINO_G, _lib.SINO_R):
+        sa = a._sino(s)
+        assert np.isfinite(sa).all() and np.abs(sa).max() > 0
+        assert np.array_equal(sa, b._sino(s))
+    assert np.array_equal(a.get_volume(), b.get_volume())
+
+
 @pytest.mark.parametrize("N,Nx", [(40, 70), (64, 64), (33, 130), (100, 300), (7, 5), (3, 1)])
 def test_tv_gradient_kernels_are_bit_identical(gpu, N, Nx):
     """Register march without row rotation (k_tv_march4, default), register march (k_tv_grad_reg), LDS march (k_tv_grad_lds)

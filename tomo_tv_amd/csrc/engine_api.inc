@@ -76,7 +76,6 @@ int tomo_destroy(tomo_engine *e)
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     if (e->aux) { (void)hipStreamSynchronize(e->aux); (void)hipStreamDestroy(e->aux); (void)hipEventDestroy(e->ev_fork); (void)hipEventDestroy(e->ev_join); }
     for (int u = 0; u < tomo_engine::MAX_CHAINS; ++u) if (e->sub_stream[u]) { (void)hipStreamSynchronize(e->sub_stream[u]); (void)hipStreamDestroy(e->sub_stream[u]); (void)hipEventDestroy(e->ev_sjoin[u]); }
-    for (int w = 0; w < 2; ++w) if (e->fp_red_stream[w]) { (void)hipStreamSynchronize(e->fp_red_stream[w]); (void)hipStreamDestroy(e->fp_red_stream[w]); for (int h = 0; h < 2; ++h) { (void)hipEventDestroy(e->ev_fp_tile[w][h]); (void)hipEventDestroy(e->ev_fp_red[w][h]); } }
     comm_release(e);
     if (e->ev_sfork) (void)hipEventDestroy(e->ev_sfork);
     if (e->ev_peer) (void)hipEventDestroy(e->ev_peer);
@@ -944,15 +943,22 @@ int tomo_fista_project_yk(tomo_engine *e, int *done)
 }
 
 // ---- scalars --------------------------------------------------------------------------------------------------------
+// A x into G and |A x - b|^2 into TOMO_S_DD on lane ln.  (A buffer allocated in here is cleared on the main stream: the caller of another
+// lane has them all in place before it forks.)
+static int data_distance_on(tomo_engine *e, const Lane &ln, int vol)
+{
+    float *x, *g; int rc;
+    if ((rc = get_vol_ro(e, vol, &x)) || (rc = get_sino(e, &e->sino[TOMO_SINO_G], &g))) return rc;
+    if ((rc = reduce_begin(e, ln))) return rc;
+    if ((rc = launch_fp_all<FP_DD>(e, ln, x, e->sino[TOMO_SINO_B], g))) return rc;
+    g_set(e, vol);                                      // FP_DD also stores g = A x
+    return reduce_end(e, ln, TOMO_S_DD);
+}
+
 int tomo_data_distance_sq(tomo_engine *e, int vol)
 {
     NEED(e);
-    float *x, *g; int rc;
-    if ((rc = get_vol_ro(e, vol, &x)) || (rc = get_sino(e, &e->sino[TOMO_SINO_G], &g))) return rc;
-    if ((rc = reduce_begin(e))) return rc;
-    if ((rc = launch_fp_all<FP_DD>(e, x, e->sino[TOMO_SINO_B], g))) return rc;
-    g_set(e, vol);                                      // FP_DD also stores g = A x
-    return reduce_end(e, TOMO_S_DD);
+    return data_distance_on(e, main_lane(e), vol);
 }
 
 // The data distance of a volume that the main sequence no longer modifies (e.g. the TEMP copy) can be evaluated on
@@ -971,12 +977,7 @@ int tomo_data_distance_sq_async(tomo_engine *e, int vol)
     if ((rc = get_vol_ro(e, vol, &tmp)) || (rc = get_sino(e, &e->sino[TOMO_SINO_G], &tmp))) return rc;   // allocate on the main stream
     HIPCHK(hipEventRecord(e->ev_fork, e->stream));
     HIPCHK(hipStreamWaitEvent(e->aux, e->ev_fork, 0));
-    hipStream_t main_stream = e->stream;
-    double *main_part = e->d_part;
-    e->stream = e->aux; e->d_part = e->d_part_aux;
-    rc = tomo_data_distance_sq(e, vol);
-    e->stream = main_stream; e->d_part = main_part;
-    if (rc) return rc;
+    if ((rc = data_distance_on(e, aux_lane(e), vol))) return rc;
     HIPCHK(hipEventRecord(e->ev_join, e->aux));
     e->async_pending = true;
     return TOMO_OK;

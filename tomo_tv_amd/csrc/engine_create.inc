@@ -102,10 +102,10 @@ static int finish_create_impl(tomo_engine *e, Coo &m, tomo_engine **out)
         build_tiles(m, e->n, e->np, FT_TY, FT_TZ, 256, t);
         static_assert(Tables::TILE_SLOTS == FT_SLOTS && Tables::TILE_BATCH == FT_BATCH, "tile stream shape");
         e->ft_tiles_z = t.tiles_z; e->ft_ntiles = t.tiles_y * t.tiles_z;
-        e->ft_nseg = t.tile_nseg;
+        e->ft.nseg = t.tile_nseg;
         std::vector<uint2> tent = pack_entries(t.tile_off.data(), t.tile_w.data(), t.tile_off.size());
         if ((rc = upload_tables(e, {tab(&e->d_ft_slot_ptr, t.tile_slot_ptr), tab(&e->d_ft_slot_seg0, t.tile_slot_seg0, 1), tab(&e->d_ft_tent, tent),
-                                    tab(&e->d_ft_rsptr, t.rseg_ptr), tab(&e->d_ft_rsidx, t.rseg_idx)}))) return rc;
+                                    tab(&e->ft.d_rsptr, t.rseg_ptr), tab(&e->ft.d_rsidx, t.rseg_idx)}))) return rc;
         release(tent); release(t.tile_off); release(t.tile_w); release(t.rseg_idx); release(t.rseg_ptr); release(t.tile_slot_ptr); release(t.tile_slot_seg0);
         lap("build_tiles + upload");
         {   // sheared-strip tables of the all-angle FP; a geometry they cannot hold (a user matrix whose rays are no lines) keeps the tile form
@@ -123,11 +123,11 @@ static int finish_create_impl(tomo_engine *e, Coo &m, tomo_engine **out)
             if (const char *env = std::getenv("TOMO_FP_STRIP")) want = std::atoi(env) != 0;
             e->fs_ok = want && build_fp_strips(m, e->n, e->np, 256, e->sxc / 64, t, why);
             if (e->fs_ok) {
-                e->fs_nitems = (int)t.fs_item.size(); e->fs_kused = t.fs_kused; e->fs_nseg = t.fs_nseg;
+                e->fs_nitems = (int)t.fs_item.size(); e->fs_kused = t.fs_kused; e->fs.nseg = t.fs_nseg;
                 static_assert(sizeof(uint2) == sizeof(uint64_t), "entry layout");
                 if ((rc = upload_tables(e, {tab(&e->d_fs_items, t.fs_item), tab(&e->d_fs_orient, t.fs_orient), tab(&e->d_fs_shift, t.fs_shift), tab(&e->d_fs_cnt, t.fs_cnt),
                                             tab(&e->d_fs_gstart, t.fs_gstart), tab(&e->d_fs_gseg0, t.fs_gseg0), tab(&e->d_fs_ent, t.fs_ent.get(), t.fs_ent_n * sizeof(uint2)),
-                                            tab(&e->d_fs_rsptr, t.fs_rseg_ptr), tab(&e->d_fs_rsidx, t.fs_rseg_idx)}))) return rc;
+                                            tab(&e->fs.d_rsptr, t.fs_rseg_ptr), tab(&e->fs.d_rsidx, t.fs_rseg_idx)}))) return rc;
                 if ((rc = dev_alloc(e, GEOMETRY, (void **)&e->d_fs_zero, 256, true))) return rc;
             }
             t.fs_ent.reset(); t.fs_ent_n = 0; release(t.fs_cnt); release(t.fs_rseg_idx); release(t.fs_rseg_ptr); release(t.fs_gstart); release(t.fs_gseg0);
@@ -146,10 +146,10 @@ static int finish_create_impl(tomo_engine *e, Coo &m, tomo_engine **out)
             // 256^3 x 60 0.138 / 0.147, 128 x 1024^2 x 120 1.58 / 1.58.  A geometry that cannot be balanced keeps the strips.
             if (e->fl_ok && !std::getenv("TOMO_FP_LIST") && t.fl_balance < 0.8) e->fl_ok = false;
             if (e->fl_ok) {
-                e->fl_nitems = (int)t.fl_item.size(); e->fl_nseg = t.fl_nseg;
+                e->fl_nitems = (int)t.fl_item.size(); e->fl.nseg = t.fl_nseg; e->fl.pairs = true;   // whole 128-slice pieces
                 if ((rc = upload_tables(e, {tab(&e->d_fl_items, t.fl_item), tab(&e->d_fl_orient, t.fl_orient), tab(&e->d_fl_shift, t.fl_shift),
                                             tab(&e->d_fl_ent, t.fl_ent.get(), t.fl_ent_n * sizeof(uint2)), tab(&e->d_fl_ptr, t.fl_ptr), tab(&e->d_fl_fent, t.fl_flush),
-                                            tab(&e->d_fl_fptr, t.fl_fptr), tab(&e->d_fl_rsptr, t.fl_rseg_ptr), tab(&e->d_fl_rsidx, t.fl_rseg_idx)}))) return rc;
+                                            tab(&e->d_fl_fptr, t.fl_fptr), tab(&e->fl.d_rsptr, t.fl_rseg_ptr), tab(&e->fl.d_rsidx, t.fl_rseg_idx)}))) return rc;
                 if ((rc = dev_alloc(e, GEOMETRY, (void **)&e->d_fl_zero, 512, true))) return rc;
             }
             t.fl_ent.reset(); t.fl_ent_n = 0; release(t.fl_flush); release(t.fl_ptr); release(t.fl_fptr); release(t.fl_rseg_ptr); release(t.fl_rseg_idx); release(t.fl_item); release(t.fl_shift);

@@ -1,5 +1,7 @@
 // engine_launch.inc -- part of tomo_engine.hip (ONE translation unit: the kernels are templates and asm blocks in headers; the host side is
-// split by topic into files that tomo_engine.hip includes in order).  This part: which kernel family runs (select_forms) and the launch helpers of the projectors, the SART steps and the all-angle back projection.
+// split by topic into files that tomo_engine.hip includes in order).  This part: which kernel family runs (select_forms) and the launch
+// helpers of the projectors, the SART steps and the all-angle back projection.  The forward projectors take the Lane they run on; the three
+// partial-sum families of the all-angle one (tile, strip, list) differ in their main kernel only and share one pass loop (fp_passes).
 
 // ---- run-time value -> template argument ----------------------------------------------------------------------
 // The ONE way a run-time value picks a kernel instantiation: f is called with a std::integral_constant of the value (the last
@@ -19,11 +21,13 @@ struct Chunks { int n, c0; };
 static Chunks chunks64(const tomo_engine *e, const Sub &sb) { return sb.nc ? Chunks{sb.nc, sb.c0} : Chunks{e->sxc / 64, 0}; }
 
 // ---- projector launches -------------------------------------------------------------------------------------
+// Every projector takes the Lane it runs on (stream, partial sums of the epilogue's scalar, scratch index); the overloads without
+// one run on the main lane.
 // lpr: 0 = wide form (64*vec slices per workgroup, scalar table walk); 16 / 32 = narrow-chunk form with that
 // many lanes per ray (k_fp_rows_g).  rowfac: the per-row factor of the epilogue.  Null means "the row sums" (d_rowsum), here and in
 // launch_fp_all: a caller that names another table passes one that exists (d_rowinner is uploaded with the geometry).
 template <int MODE>
-static int launch_fp(tomo_engine *e, const float *x, int row0, int nrows, const float *b, float *out, int lpr = 0, const float *rowfac = nullptr)
+static int launch_fp(tomo_engine *e, const Lane &ln, const float *x, int row0, int nrows, const float *b, float *out, int lpr = 0, const float *rowfac = nullptr)
 {
     if (!rowfac) rowfac = e->d_rowsum;
     if (lpr == 16 || lpr == 32) {
@@ -32,7 +36,7 @@ static int launch_fp(tomo_engine *e, const float *x, int row0, int nrows, const 
         int64_t waves = (int64_t)((nrows + R - 1) / R) * nchunk;
         dim3 grid((unsigned)((waves + 3) / 4)), block(256);
         with_int<16, 32>(lpr, [&](auto L) {
-            hipLaunchKernelGGL((k_fp_rows_g<L(), MODE>), grid, block, 0, e->stream, x, e->d_rptr, e->d_rent, b, rowfac, out, e->d_part, row0, nrows, e->sx, nchunk);
+            hipLaunchKernelGGL((k_fp_rows_g<L(), MODE>), grid, block, 0, ln.stream, x, e->d_rptr, e->d_rent, b, rowfac, out, ln.part, row0, nrows, e->sx, nchunk);
         });
         LAUNCHCHK();
         return TOMO_OK;
@@ -41,22 +45,27 @@ static int launch_fp(tomo_engine *e, const float *x, int row0, int nrows, const 
     int nchunk = e->sxc / (64 * vec);
     dim3 grid((unsigned)((int64_t)nrows * nchunk)), block(256);
     with_vec(vec, [&](auto V) {
-        hipLaunchKernelGGL((k_fp_rows<V(), MODE>), grid, block, 0, e->stream, x, e->d_rptr, e->d_rent, b, rowfac, out, e->d_part, row0, nrows, e->sx);
+        hipLaunchKernelGGL((k_fp_rows<V(), MODE>), grid, block, 0, ln.stream, x, e->d_rptr, e->d_rent, b, rowfac, out, ln.part, row0, nrows, e->sx);
     });
     LAUNCHCHK();
     return TOMO_OK;
 }
-
 template <int MODE>
-static void launch_fp_reduce(tomo_engine *e, hipStream_t rs, const float *part, const uint32_t *rsptr, const uint32_t *rsidx, const float *b,
-                             const float *rowfac, float *out, int c0, int ncp)
+static int launch_fp(tomo_engine *e, const float *x, int row0, int nrows, const float *b, float *out, int lpr = 0, const float *rowfac = nullptr)
+{
+    return launch_fp<MODE>(e, main_lane(e), x, row0, nrows, b, out, lpr, rowfac);
+}
+
+// the row sums of chunks [c0, c0 + ncp) from the family's partial sums in the lane's scratch
+template <int MODE>
+static void launch_fp_reduce(tomo_engine *e, const Lane &ln, const FpFamily &f, const float *b, const float *rowfac, float *out, int c0, int ncp)
 {
     int lpr = (ncp % 4 == 0) ? 64 : (ncp % 2 == 0) ? 32 : 16;
     int64_t items = (int64_t)e->nrows * (ncp * 16 / lpr);
     int64_t waves = (items + 64 / lpr - 1) / (64 / lpr);
     dim3 grid((unsigned)((waves + 3) / 4)), block(256);
     with_int<64, 32, 16>(lpr, [&](auto L) {
-        hipLaunchKernelGGL((k_fp_tile_reduce<L(), MODE>), grid, block, 0, rs, part, rsptr, rsidx, b, rowfac, out, e->d_part, (int)e->nrows, e->sx, c0, ncp);
+        hipLaunchKernelGGL((k_fp_tile_reduce<L(), MODE>), grid, block, 0, ln.stream, f.part[ln.idx], f.d_rsptr, f.d_rsidx, b, rowfac, out, ln.part, (int)e->nrows, e->sx, c0, ncp);
     });
 }
 
@@ -73,72 +82,83 @@ static int plan_ncp(const tomo_engine *e, uint32_t nseg, bool pairs)
     return pairs || ncp >= 2 ? 2 : ncp;
 }
 
-// That scratch: one buffer per stream that projects (fp_which = 1: the second stream), `chunks` chunks large, allocated on first use.
-static int fp_which(const tomo_engine *e) { return (e->aux && e->stream == e->aux) ? 1 : 0; }
-static int fp_scratch(tomo_engine *e, float **slot, uint32_t nseg, size_t chunks)
+// the options that plan_ncp reads may change until a scratch has been sized by them
+static bool fp_scratch_exists(const tomo_engine *e)
 {
-    if (*slot) return TOMO_OK;
-    return dev_alloc(e, GEOMETRY, (void **)slot, (size_t)std::max<uint32_t>(1, nseg) * chunks * 64 * sizeof(float), false);
+    for (const FpFamily *f : {&e->ft, &e->fs, &e->fl}) if (f->part[0] || f->part[1]) return true;
+    return false;
+}
+static void fp_forget_plans(tomo_engine *e) { e->ft.ncp = e->fs.ncp = e->fl.ncp = 0; }
+
+// The pass loop of the three families: the slab's chunks in passes of f.ncp (planned here on first use), each pass the family's main
+// kernel -- launch_main(part, c0, ncp) writes the partial sums of chunks [c0, c0 + ncp) -- and then the reduce with the epilogue,
+// both on the lane's stream.  The scratch is one pass large, one per lane that projects, allocated on that lane's first use.
+template <int MODE, class F>
+static int fp_passes(tomo_engine *e, const Lane &ln, FpFamily &f, const float *b, const float *rowfac, float *out, F &&launch_main)
+{
+    const int nchunk = e->sxc / 64;
+    if (!f.ncp) f.ncp = plan_ncp(e, f.nseg, f.pairs);
+    float *&part = f.part[ln.idx];
+    if (!part) {
+        if (int rc = dev_alloc(e, GEOMETRY, (void **)&part, (size_t)std::max<uint32_t>(1, f.nseg) * f.ncp * 64 * sizeof(float), false)) return rc;
+    }
+    for (int c0 = 0; c0 < nchunk; c0 += f.ncp) {
+        const int ncp = std::min(f.ncp, nchunk - c0);              // (pairs: even, the slab is whole 128-slice pieces)
+        {
+            ProfScope ps(e, TOMO_K_FP_TILE, ln.stream);
+            launch_main(part, c0, ncp);
+            LAUNCHCHK();
+        }
+        {
+            ProfScope ps(e, TOMO_K_FP_REDUCE, ln.stream);
+            launch_fp_reduce<MODE>(e, ln, f, b, rowfac, out, c0, ncp);
+            LAUNCHCHK();
+        }
+    }
+    return TOMO_OK;
+}
+
+// all-angle FP, tile-stationary form (k_fp_tile + k_fp_tile_reduce)
+template <int MODE>
+static int launch_fp_tile(tomo_engine *e, const Lane &ln, const float *x, const float *b, float *out, const float *rowfac)
+{
+    if (!e->attr_fp) {   // per engine: the attribute belongs to the (function, device) pair
+        HIPCHK(hipFuncSetAttribute((const void *)k_fp_tile, hipFuncAttributeMaxDynamicSharedMemorySize, FT_LDS_BYTES));
+        e->attr_fp = true;
+    }
+    return fp_passes<MODE>(e, ln, e->ft, b, rowfac, out, [&](float *part, int c0, int ncp) {
+        dim3 grid((unsigned)(8 * ((e->ft_ntiles + 7) / 8) * ncp)), block(FT_THREADS);
+        hipLaunchKernelGGL(k_fp_tile, grid, block, FT_LDS_BYTES, ln.stream, x, e->d_ft_slot_ptr, e->d_ft_slot_seg0, e->d_ft_tent, part,
+                           e->n, e->sx, e->ft_tiles_z, e->ft_ntiles, c0, ncp);
+    });
 }
 
 // all-angle FP, sheared-strip form (k_fp_strip + k_fp_tile_reduce on the strips' row lists)
 template <int MODE>
-static int launch_fp_strip(tomo_engine *e, const float *x, const float *b, float *out, const float *rowfac)
+static int launch_fp_strip(tomo_engine *e, const Lane &ln, const float *x, const float *b, float *out, const float *rowfac)
 {
-    const int nchunk = e->sxc / 64;
-    if (!e->fs_ncp) e->fs_ncp = plan_ncp(e, e->fs_nseg, false);
-    float **slot = fp_which(e) ? &e->fs_part_aux : &e->fs_part;
-    if (int rc = fp_scratch(e, slot, e->fs_nseg, e->fs_ncp)) return rc;
-    float *part = *slot;
-    for (int c0 = 0; c0 < nchunk; c0 += e->fs_ncp) {
-        const int ncp = std::min(e->fs_ncp, nchunk - c0);
-        {
-            ProfScope ps(e, TOMO_K_FP_TILE);
-            dim3 grid((unsigned)(8 * ((e->fs_nitems + 7) / 8) * ncp)), block(FS_THREADS);
-            with_int<8, 12, 16>(e->fs_kused <= 8 ? 8 : e->fs_kused <= 12 ? 12 : 16, [&](auto K) {
-                hipLaunchKernelGGL((k_fp_strip<K()>), grid, block, 0, e->stream, x, e->d_fs_items, e->d_fs_orient, e->d_fs_shift, e->d_fs_cnt,
-                                   e->d_fs_gstart, e->d_fs_gseg0, e->d_fs_ent, part, e->n, e->sx, e->fs_nitems, c0, ncp, e->d_fs_zero);
-            });
-            LAUNCHCHK();
-        }
-        {
-            ProfScope ps(e, TOMO_K_FP_REDUCE);
-            launch_fp_reduce<MODE>(e, e->stream, part, e->d_fs_rsptr, e->d_fs_rsidx, b, rowfac, out, c0, ncp);
-            LAUNCHCHK();
-        }
-    }
-    return TOMO_OK;
+    return fp_passes<MODE>(e, ln, e->fs, b, rowfac, out, [&](float *part, int c0, int ncp) {
+        dim3 grid((unsigned)(8 * ((e->fs_nitems + 7) / 8) * ncp)), block(FS_THREADS);
+        with_int<8, 12, 16>(e->fs_kused <= 8 ? 8 : e->fs_kused <= 12 ? 12 : 16, [&](auto K) {
+            hipLaunchKernelGGL((k_fp_strip<K()>), grid, block, 0, ln.stream, x, e->d_fs_items, e->d_fs_orient, e->d_fs_shift, e->d_fs_cnt,
+                               e->d_fs_gstart, e->d_fs_gseg0, e->d_fs_ent, part, e->n, e->sx, e->fs_nitems, c0, ncp, e->d_fs_zero);
+        });
+    });
 }
 
 // all-angle FP, sheared strips as wave-uniform entry lists (k_fp_list + k_fp_tile_reduce on the lists' row lists)
 template <int MODE>
-static int launch_fp_list(tomo_engine *e, const float *x, const float *b, float *out, const float *rowfac)
+static int launch_fp_list(tomo_engine *e, const Lane &ln, const float *x, const float *b, float *out, const float *rowfac)
 {
-    const int nchunk = e->sxc / 64;
-    if (!e->fl_ncp) e->fl_ncp = plan_ncp(e, e->fl_nseg, true);      // whole 128-slice pieces
     if (!e->attr_fl) {
         HIPCHK(hipFuncSetAttribute((const void *)k_fp_list, hipFuncAttributeMaxDynamicSharedMemorySize, FL_LDS_BYTES));
         e->attr_fl = true;
     }
-    float **slot = fp_which(e) ? &e->fl_part_aux : &e->fl_part;
-    if (int rc = fp_scratch(e, slot, e->fl_nseg, e->fl_ncp)) return rc;
-    float *part = *slot;
-    for (int c0 = 0; c0 < nchunk; c0 += e->fl_ncp) {
-        const int ncp = std::min(e->fl_ncp, nchunk - c0);            // even: the slab is whole 128-slice pieces
-        {
-            ProfScope ps(e, TOMO_K_FP_TILE);
-            dim3 grid((unsigned)(8 * ((e->fl_nitems + 7) / 8) * (ncp / 2))), block(FL_THREADS);
-            hipLaunchKernelGGL(k_fp_list, grid, block, FL_LDS_BYTES, e->stream, x, e->d_fl_items, e->d_fl_orient, e->d_fl_shift, e->d_fl_ent, e->d_fl_ptr,
-                               e->d_fl_fent, e->d_fl_fptr, part, e->n, e->sx, e->fl_nitems, c0 / 2, ncp / 2, ncp, e->d_fl_zero);
-            LAUNCHCHK();
-        }
-        {
-            ProfScope ps(e, TOMO_K_FP_REDUCE);
-            launch_fp_reduce<MODE>(e, e->stream, part, e->d_fl_rsptr, e->d_fl_rsidx, b, rowfac, out, c0, ncp);
-            LAUNCHCHK();
-        }
-    }
-    return TOMO_OK;
+    return fp_passes<MODE>(e, ln, e->fl, b, rowfac, out, [&](float *part, int c0, int ncp) {
+        dim3 grid((unsigned)(8 * ((e->fl_nitems + 7) / 8) * (ncp / 2))), block(FL_THREADS);
+        hipLaunchKernelGGL(k_fp_list, grid, block, FL_LDS_BYTES, ln.stream, x, e->d_fl_items, e->d_fl_orient, e->d_fl_shift, e->d_fl_ent, e->d_fl_ptr,
+                           e->d_fl_fent, e->d_fl_fptr, part, e->n, e->sx, e->fl_nitems, c0 / 2, ncp / 2, ncp, e->d_fl_zero);
+    });
 }
 
 // ---- which form runs ---------------------------------------------------------------------------------------------------------
@@ -172,78 +192,22 @@ static Forms select_forms(const tomo_engine *e)
     return f;
 }
 
-// all-angle FP: sheared-strip form, else the tile-stationary form (k_fp_tile + k_fp_tile_reduce) unless switched off, else the ray-driven form
+// all-angle FP in the form select_forms names
+template <int MODE>
+static int launch_fp_all(tomo_engine *e, const Lane &ln, const float *x, const float *b, float *out, const float *rowfac = nullptr)
+{
+    if (!rowfac) rowfac = e->d_rowsum;
+    switch (select_forms(e).fp) {
+    case TOMO_FORM_FP_LIST: return launch_fp_list<MODE>(e, ln, x, b, out, rowfac);
+    case TOMO_FORM_FP_STRIP: return launch_fp_strip<MODE>(e, ln, x, b, out, rowfac);
+    case TOMO_FORM_FP_TILE: return launch_fp_tile<MODE>(e, ln, x, b, out, rowfac);
+    default: return launch_fp<MODE>(e, ln, x, 0, (int)e->nrows, b, out, e->fp_all_lpr, rowfac);
+    }
+}
 template <int MODE>
 static int launch_fp_all(tomo_engine *e, const float *x, const float *b, float *out, const float *rowfac = nullptr)
 {
-    if (!rowfac) rowfac = e->d_rowsum;
-    const int form = select_forms(e).fp;
-    if (form == TOMO_FORM_FP_LIST) return launch_fp_list<MODE>(e, x, b, out, rowfac);
-    if (form == TOMO_FORM_FP_STRIP) return launch_fp_strip<MODE>(e, x, b, out, rowfac);
-    if (form == TOMO_FORM_FP_ROWS) return launch_fp<MODE>(e, x, 0, (int)e->nrows, b, out, e->fp_all_lpr, rowfac);
-    const int nchunk = e->sxc / 64;
-    if (!e->ft_ncp) {
-        e->ft_ncp = plan_ncp(e, e->ft_nseg, false);
-        if (!e->attr_fp) {   // per engine: the attribute belongs to the (function, device) pair
-            HIPCHK(hipFuncSetAttribute((const void *)k_fp_tile, hipFuncAttributeMaxDynamicSharedMemorySize, FT_LDS_BYTES));
-            e->attr_fp = true;
-        }
-    }
-    // The tile kernel is LDS / vector-ALU bound and WRITES the partial sums; the reduce kernel is HBM-read bound.  With
-    // "fp_tile_pipe" = P >= 2 the projection runs as P groups of chunks, the reduce of group k on a helper stream beside the tile
-    // kernel of group k+1 (two halves of the scratch, events both ways): the two kernels want different parts of the chip.
-    // Built and measured in round 3 -- and it buys nothing (numbers at the option's declaration): the tile kernel's one 1024-thread
-    // workgroup per CU leaves room for one reduce wave per SIMD, which reads no faster than the tile kernel's own stores leave
-    // the memory system idle.  Kept as an option, default off.
-    int ncp_call = e->ft_ncp, pipe = 0;
-    if (e->fp_tile_pipe >= 2 && nchunk >= 2 * 2) {          // groups of at least two chunks (64-lane reduce spans)
-        int P = std::min(e->fp_tile_pipe, nchunk / 2);
-        int per = (nchunk + P - 1) / P;
-        per = (per + 1) & ~1;
-        if (per <= e->ft_ncp && per < nchunk) { ncp_call = per; pipe = 1; }
-    }
-    // sized for both schemes: one pass of ft_ncp chunks, or two halves of a pipelined group each
-    const int which = fp_which(e);
-    float **slot = which ? &e->ft_part_aux : &e->ft_part;
-    if (int rc = fp_scratch(e, slot, e->ft_nseg, std::max<size_t>(e->ft_ncp, 2 * (size_t)((((e->sxc / 64 + 1) / 2) + 1) & ~1)))) return rc;
-    if (pipe && !e->fp_red_stream[which]) {
-        HIPCHK(hipStreamCreateWithFlags(&e->fp_red_stream[which], hipStreamNonBlocking));
-        for (int h = 0; h < 2; ++h) {
-            HIPCHK(hipEventCreateWithFlags(&e->ev_fp_tile[which][h], hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&e->ev_fp_red[which][h], hipEventDisableTiming));
-        }
-    }
-    const size_t half_elems = (size_t)std::max<uint32_t>(1, e->ft_nseg) * ncp_call * 64;
-    int k = 0;
-    for (int c0 = 0; c0 < nchunk; c0 += ncp_call, ++k) {
-        int ncp = std::min(ncp_call, nchunk - c0);
-        const int half = k & 1;
-        float *part = *slot + (pipe ? half * half_elems : 0);
-        hipStream_t rs = pipe ? e->fp_red_stream[which] : e->stream;
-        if (pipe && k >= 2) HIPCHK(hipStreamWaitEvent(e->stream, e->ev_fp_red[which][half], 0));   // this half of the scratch is free again
-        {
-            ProfScope ps(e, TOMO_K_FP_TILE);
-            dim3 grid((unsigned)(8 * ((e->ft_ntiles + 7) / 8) * ncp)), block(FT_THREADS);
-            hipLaunchKernelGGL(k_fp_tile, grid, block, FT_LDS_BYTES, e->stream, x, e->d_ft_slot_ptr, e->d_ft_slot_seg0, e->d_ft_tent, part,
-                               e->n, e->sx, e->ft_tiles_z, e->ft_ntiles, c0, ncp);
-            LAUNCHCHK();
-        }
-        if (pipe) {
-            HIPCHK(hipEventRecord(e->ev_fp_tile[which][half], e->stream));
-            HIPCHK(hipStreamWaitEvent(rs, e->ev_fp_tile[which][half], 0));
-        }
-        {
-            ProfScope ps(e, TOMO_K_FP_REDUCE, rs);
-            launch_fp_reduce<MODE>(e, rs, part, e->d_ft_rsptr, e->d_ft_rsidx, b, rowfac, out, c0, ncp);
-            LAUNCHCHK();
-        }
-        if (pipe) HIPCHK(hipEventRecord(e->ev_fp_red[which][half], rs));
-    }
-    if (pipe) {                                             // the projection is complete on the caller's stream
-        HIPCHK(hipStreamWaitEvent(e->stream, e->ev_fp_red[which][0], 0));
-        if (k >= 2) HIPCHK(hipStreamWaitEvent(e->stream, e->ev_fp_red[which][1], 0));
-    }
-    return TOMO_OK;
+    return launch_fp_all<MODE>(e, main_lane(e), x, b, out, rowfac);
 }
 
 // residual rows from a projection already in G (fp_reuse)

@@ -49,7 +49,6 @@ int tomo_set_option(tomo_engine *e, const char *name, int value)
     if (std::strcmp(name, "sart_resident_spin") == 0) { e->rs_spin_limit = value < 0 ? (1u << 21) : (uint32_t)value; return TOMO_OK; }   // polls before a wait gives up (< 0: the default; tests: tiny, 0 = at the first look)
     if (std::strcmp(name, "sart_resident_test_fail") == 0) { e->rs_test_fail = std::max(0, value); return TOMO_OK; }   // tests: chunk + 1 that refuses to commit
     if (std::strcmp(name, "fp_reuse") == 0) { e->fp_reuse = value != 0; g_clear(e); e->yk_claim.valid = false; return TOMO_OK; }
-    if (std::strcmp(name, "fp_tile_pipe") == 0) { e->fp_tile_pipe = std::max(0, value); return TOMO_OK; }
     if (std::strcmp(name, "sart_streams") == 0) { e->sart_streams = value >= 2 ? std::min(value, (int)tomo_engine::MAX_CHAINS) : (value == 1 ? 1 : 0); return TOMO_OK; }
     if (std::strcmp(name, "art_tile") == 0) { e->art_tile = value ? 1 : 0; return TOMO_OK; }
     if (std::strcmp(name, "sart_skip_same") == 0) { e->sart_skip_same = value ? 1 : 0; return TOMO_OK; }
@@ -65,12 +64,12 @@ int tomo_set_option(tomo_engine *e, const char *name, int value)
     if (std::strcmp(name, "fp_strip") == 0) { e->fp_strip = value ? 1 : 0; return TOMO_OK; }
     if (std::strcmp(name, "fp_tile") == 0) { e->fp_tile = value ? 1 : 0; e->fp_strip = 0; return TOMO_OK; }
     if (std::strcmp(name, "fp_tile_chunks_per_pass") == 0) {   // any count >= 1 (0 = from the scratch cap); before the first projection
-        if (value < 0 || e->ft_part || e->ft_part_aux || e->fs_part || e->fs_part_aux || e->fl_part || e->fl_part_aux) return fail(TOMO_ERR_STATE, "fp_tile_chunks_per_pass must be set before the first projection");
-        e->ft_ncp_forced = value; e->ft_ncp = 0; e->fs_ncp = 0; e->fl_ncp = 0; return TOMO_OK;
+        if (value < 0 || fp_scratch_exists(e)) return fail(TOMO_ERR_STATE, "fp_tile_chunks_per_pass must be set before the first projection");
+        e->ft_ncp_forced = value; fp_forget_plans(e); return TOMO_OK;
     }
     if (std::strcmp(name, "fp_tile_scratch_mib") == 0) {   // cap of the partial-sum scratch; takes effect before the first all-angle FP
-        if (value <= 0 || e->ft_part || e->ft_part_aux || e->fs_part || e->fs_part_aux || e->fl_part || e->fl_part_aux) return fail(TOMO_ERR_STATE, "fp_tile_scratch_mib must be positive and set before the first projection");
-        e->ft_scratch_cap = (size_t)value << 20; e->ft_ncp = 0; e->fs_ncp = 0; e->fl_ncp = 0; return TOMO_OK;
+        if (value <= 0 || fp_scratch_exists(e)) return fail(TOMO_ERR_STATE, "fp_tile_scratch_mib must be positive and set before the first projection");
+        e->ft_scratch_cap = (size_t)value << 20; fp_forget_plans(e); return TOMO_OK;
     }
     if (std::strcmp(name, "tv_gnorm_slot") == 0) {
         if (value < 0 || value >= TOMO_S_COUNT) return fail(TOMO_ERR_ARG, "bad scalar slot");

@@ -123,7 +123,7 @@ int tomo_tv_partial(tomo_engine *e, int vol, float eps)
     }
     // the march of the gradient kernels without their gradient half: x is read once
     if (!e->d_part_tv) { if ((rc = dev_alloc(e, ENGINE, (void **)&e->d_part_tv, NPART * sizeof(double), true))) return rc; }
-    if ((rc = part_begin(e, e->d_part_tv))) return rc;
+    if ((rc = reduce_begin(e, tv_lane(e)))) return rc;
     const int yseg = 32;
     if (e->tv_lds == 1 && e->tv_march4 && e->nx % 64 == 0 && e->n % 8 == 0) {
         // the value alone from the branch-free march (round 3): the R loop without the gradient half
@@ -135,7 +135,7 @@ int tomo_tv_partial(tomo_engine *e, int vol, float eps)
         hipLaunchKernelGGL((k_tv_grad_lds<8, true, false>), grid, dim3(256), 0, e->stream, x, h, (float *)nullptr, (double *)nullptr, eps, e->n, e->nx, e->sx, yseg, e->d_part_tv);
     }
     LAUNCHCHK();
-    return part_end(e, e->d_part_tv, TOMO_S_TV);
+    return reduce_end(e, tv_lane(e), TOMO_S_TV);
 }
 
 // Rows a wave of the register march walks.  32 at a full slab (8 chunks x 64 z-blocks x 16 segments = 8192 waves at 512^3);
@@ -162,7 +162,7 @@ static int tv_grad_impl(tomo_engine *e, float eps, bool with_tv, float *g_first 
     if (with_tv && e->tv_lds != 8 && e->tv_lds != 1) with_tv = false;
     if (with_tv) {
         if (!e->d_part_tv) { if ((rc = dev_alloc(e, ENGINE, (void **)&e->d_part_tv, NPART * sizeof(double), true))) return rc; }
-        if ((rc = part_begin(e, e->d_part_tv))) return rc;
+        if ((rc = reduce_begin(e, tv_lane(e)))) return rc;
     }
     {
         ProfScope ps(e, TOMO_K_TV_GRAD);
@@ -204,7 +204,7 @@ static int tv_grad_impl(tomo_engine *e, float eps, bool with_tv, float *g_first 
         }
     }
     LAUNCHCHK();
-    if (with_tv && (rc = part_end(e, e->d_part_tv, TOMO_S_TV))) return rc;
+    if (with_tv && (rc = reduce_end(e, tv_lane(e), TOMO_S_TV))) return rc;
     return reduce_end(e, TOMO_S_GNORM);
 }
 

@@ -117,6 +117,17 @@ struct ChainHelper {
 static int pool_alloc(void **p, size_t bytes) { HIPCHK(hipMalloc(p, bytes)); return TOMO_OK; }
 static void pool_free(void *p) { (void)hipFree(p); }
 
+// One partial-sum family of the all-angle forward projector (k_fp_tile / k_fp_strip / k_fp_list): the main kernel writes nseg
+// partial row sums per 64-slice chunk into the scratch of the lane it runs on, k_fp_tile_reduce gathers them through the row
+// lists rsptr / rsidx.  ncp chunks go into one pass (planned on first use, plan_ncp; 0 = not planned yet) and size the scratch.
+struct FpFamily {
+    uint32_t nseg = 0;
+    int ncp = 0;
+    bool pairs = false;                           // works on whole pairs of chunks (128-slice pieces)
+    float *part[2] = {nullptr, nullptr};          // scratch, [lane]: allocated when that lane first projects
+    uint32_t *d_rsptr = nullptr, *d_rsidx = nullptr;
+};
+
 struct CommRef;
 struct tomo_engine;
 static void comm_release(tomo_engine *e);
@@ -162,36 +173,30 @@ struct tomo_engine {
     bool seg_ready = false;                       // the walk / segment tables above are on the device (built at creation or on first use)
     std::vector<double> angles;                   // the tilt angles of an engine created from angles (tomo_create): tables built on first use come from them
     float *sart_alt = nullptr;                    // ping-pong partner of the volume being swept
-    // tile-stationary all-angle FP (k_fp_tile): tables, partial-sum scratch (one per stream that can run it)
+    // tile-stationary all-angle FP (k_fp_tile): its family record and tables; k_bp_tile walks the same tile grid (ft_tiles_z, ft_ntiles)
     int fp_tile = 1, ft_tiles_z = 0, ft_ntiles = 0;
-    uint32_t ft_nseg = 0;
-    uint32_t *d_ft_slot_ptr = nullptr, *d_ft_slot_seg0 = nullptr, *d_ft_rsptr = nullptr, *d_ft_rsidx = nullptr;
+    FpFamily ft;
+    uint32_t *d_ft_slot_ptr = nullptr, *d_ft_slot_seg0 = nullptr;
     uint2 *d_ft_tent = nullptr;
-    float *ft_part = nullptr, *ft_part_aux = nullptr;
     // sheared-strip all-angle FP (k_fp_strip, round 4): ray sums resident in registers, ~5 partial sums per ray instead of ~27
-    int fp_strip = 1, fs_nitems = 0, fs_kused = 0, fs_ncp = 0;
-    bool fs_ok = false, attr_fs = false;
-    uint32_t fs_nseg = 0;
+    int fp_strip = 1, fs_nitems = 0, fs_kused = 0;
+    bool fs_ok = false;
+    FpFamily fs;
     FsItemD *d_fs_items = nullptr;
     int *d_fs_orient = nullptr, *d_fs_shift = nullptr;
     uint4 *d_fs_cnt = nullptr;
-    uint32_t *d_fs_gstart = nullptr, *d_fs_gseg0 = nullptr, *d_fs_rsptr = nullptr, *d_fs_rsidx = nullptr;
+    uint32_t *d_fs_gstart = nullptr, *d_fs_gseg0 = nullptr;
     uint2 *d_fs_ent = nullptr;
     float *d_fs_zero = nullptr;                   // 256 bytes of zeros: what a strip tile's pixels outside the image are staged from
-    float *fs_part = nullptr, *fs_part_aux = nullptr;
     // ... and as wave-uniform entry lists (k_fp_list) when the slab is a whole number of 128-slice pieces
-    int fp_list = 1, fl_nitems = 0, fl_ncp = 0;
+    int fp_list = 1, fl_nitems = 0;
     bool fl_ok = false, attr_fl = false;
-    uint32_t fl_nseg = 0;
+    FpFamily fl;
     FlItemD *d_fl_items = nullptr;
     int *d_fl_orient = nullptr, *d_fl_shift = nullptr;
     uint2 *d_fl_ent = nullptr, *d_fl_fent = nullptr;
-    uint32_t *d_fl_ptr = nullptr, *d_fl_fptr = nullptr, *d_fl_rsptr = nullptr, *d_fl_rsidx = nullptr;
-    float *d_fl_zero = nullptr, *fl_part = nullptr, *fl_part_aux = nullptr;
-    // all-angle FP as a two-stage pipeline over groups of 64-slice chunks ("fp_tile_pipe"): [0] main stream, [1] second stream
-    int fp_tile_pipe = 0;   // off: measured (round 3) 1.50 vs 1.52 ms at 512^3 x 90, 1.91 vs 1.83 ms at 128 x 1024^2 x 120, 0.127 vs 0.154 ms at 256^3 x 60
-    hipStream_t fp_red_stream[2] = {nullptr, nullptr};
-    hipEvent_t ev_fp_tile[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}, ev_fp_red[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    uint32_t *d_fl_ptr = nullptr, *d_fl_fptr = nullptr;
+    float *d_fl_zero = nullptr;
     bool attr_fp = false, attr_bp = false, attr_st = false;   // dynamic-LDS limits raised on this engine's device
     // The SART chain of one slab is a string of dependent launches (tile step -> residual finish -> tile step ...): ~5.7 us of
     // idle chip after each and a tail of partly filled CUs at the end of each.  Slices are independent, so the sweep CAN run as
@@ -266,7 +271,7 @@ struct tomo_engine {
     bool fb_ok = false;
     uint4 *d_fb_cell = nullptr;
     uint32_t *d_fb_win = nullptr;
-    int ft_ncp = 0, ft_ncp_forced = 0;            // slice chunks per pass (bounds the scratch); forced value for tests
+    int ft_ncp_forced = 0;                        // chunks per pass of every FP family, forced (tests); 0 = what ft_scratch_cap holds
     size_t ft_scratch_cap = (size_t)8 << 30;      // >= 4 chunks per pass up to 1024^2 x 120 (one pass measured 12 % faster than one chunk per pass)
     // fields
     float *vol[TOMO_VOL_SLOTS] = {};
@@ -296,7 +301,7 @@ struct tomo_engine {
     double *h_snap = nullptr;          // pinned: tomo_scalars_snapshot
     hipEvent_t ev_snap = nullptr;
     bool snap_pending = false;
-    bool part_open[3] = {false, false, false};   // main / aux / tv partial sums: a reduction is in flight (see part_begin)
+    bool part_open[3] = {false, false, false};   // [Lane::idx]: a reduction into that lane's partial sums is in flight (see reduce_begin)
     hipStream_t aux = nullptr;                    // second stream for work that is independent of the main sequence
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool async_pending = false;
@@ -445,6 +450,15 @@ struct Sub {
 static int sub_vec(const tomo_engine *e, const Sub &sb) { return sb.nc && sb.vec ? sb.vec : e->vec; }
 static Sub whole(const tomo_engine *e) { return Sub{e->stream, e->sub_c0, e->sub_nc}; }
 
+// Where a projection or a reduction of the whole slab runs: the stream, the partial sums its scalar is gathered in, and the index that
+// picks the lane's FP scratch (FpFamily::part) and its open flag (part_open).  Passed explicitly: the main sequence and the evaluation
+// on the second stream (tomo_data_distance_sq_async) go through the same launchers side by side.  The TV sum is a second reduction
+// of the main stream that is open at the same time as the main one: a lane of its own that never projects.
+struct Lane { hipStream_t stream; double *part; int idx; };
+static Lane main_lane(const tomo_engine *e) { return Lane{e->stream, e->d_part, 0}; }
+static Lane aux_lane(const tomo_engine *e) { return Lane{e->aux, e->d_part_aux, 1}; }
+static Lane tv_lane(const tomo_engine *e) { return Lane{e->stream, e->d_part_tv, 2}; }
+
 struct ProfScope {
     tomo_engine *e; int k; hipEvent_t stop = nullptr; hipStream_t st;
     // key >= 0: the launch's position in its chain (the two sub-slab chains of a SART sweep then bracket the SAME links, so
@@ -476,26 +490,22 @@ struct ProfScope {
 // The partial-sum buffers are zero between reductions: they are allocated zeroed and k_finalize clears what it has read,
 // so a reduction costs no memset launch.  Only a reduction that was abandoned half-way (an error return between begin
 // and end) leaves its buffer marked open, and the next begin clears it.
-static bool &part_open(tomo_engine *e, const double *part)
+static int reduce_begin(tomo_engine *e, const Lane &ln)
 {
-    return part == e->d_part_tv ? e->part_open[2] : part == e->d_part_aux ? e->part_open[1] : e->part_open[0];
-}
-static int part_begin(tomo_engine *e, double *part)
-{
-    bool &open = part_open(e, part);
-    if (open) HIPCHK(hipMemsetAsync(part, 0, NPART * sizeof(double), e->stream));
+    bool &open = e->part_open[ln.idx];
+    if (open) HIPCHK(hipMemsetAsync(ln.part, 0, NPART * sizeof(double), ln.stream));
     open = true;
     return TOMO_OK;
 }
-static int part_end(tomo_engine *e, double *part, int slot)
+static int reduce_end(tomo_engine *e, const Lane &ln, int slot)
 {
-    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(NPART), 0, e->stream, part, e->d_scal + slot);
+    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(NPART), 0, ln.stream, ln.part, e->d_scal + slot);
     LAUNCHCHK();
-    part_open(e, part) = false;
+    e->part_open[ln.idx] = false;
     return TOMO_OK;
 }
-static int reduce_begin(tomo_engine *e) { return part_begin(e, e->d_part); }
-static int reduce_end(tomo_engine *e, int slot) { return part_end(e, e->d_part, slot); }
+static int reduce_begin(tomo_engine *e) { return reduce_begin(e, main_lane(e)); }
+static int reduce_end(tomo_engine *e, int slot) { return reduce_end(e, main_lane(e), slot); }
 
 constexpr int TV_YSEG_MIN = 8, TV_WAVES_WANTED = 4096;   // round 3: the march holds 4 waves per SIMD = 4096 resident waves: one full round
                                                          // (8192 before; 128 slices: 16 rows per wave 94.5 us per inner iteration against 8 rows ~100)
