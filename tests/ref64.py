@@ -23,6 +23,14 @@ Bounds (u = 2^-24, gamma_m = m u / (1 - m u)):
   ``tv_gnorm``), the fusion steps (``mm_model``, ``mm_update``) and the host's Lipschitz constants: first-order worst-case bounds,
   stated with each function.  Those built on device transcendentals use ``LOGF_ULP``, ``C_EXP`` and ``C_LOG``, which are
   assumptions about the device's logf / exp2f / log2f, not measurements.  ``proj_max`` / ``proj_scale`` are exact.
+* CGLS (``tomo_cgls``: per-slice alpha and beta).  One step from a zero volume has an a-priori first-order bound
+  (``Matrix.cgls_first_step``: there r = b exactly and the chain is BP, two slice sums, a ratio and one axpy); several steps are
+  sequential (``Matrix.cgls`` against ``cgls_f32`` under ``seq_bound``).  ``cgls_sino`` builds a sinogram whose per-slice alpha
+  differ between neighbouring slices by far more than their bound (``alpha_separation``): a coefficient read from the wrong
+  slice cannot hide.
+* The WBP row filter (``filter_rows``): ``gamma(N + 1) sum_k |h| |in|`` per element, any order, any FMA use.
+* The FISTA passes.  ``soft_threshold`` is the exact float32 result; ``momentum`` / ``sino_extrapolate`` (y = r + beta (r - old))
+  carry one rounding each for the difference, the product and the sum (the last two one rounding under FMA contraction).
 """
 import numpy as np
 
@@ -303,6 +311,205 @@ class Matrix:
             a = (b[:, j] - x[:, c] @ w) / self.rowinner[j]
             x[:, c] += beta * a[:, None] * w[None, :]
         return np.maximum(x, 0.0).reshape(len(x), self.N, self.N)
+
+    # ---- CGLS (tomo_cgls: k_slice_sumsq, k_slice_sumsq_finish, k_slice_ratio, k_slice_axpy, k_slice_xpay) ----------------------------
+    def cgls(self, x0, b, niter, slices=None):
+        """``niter`` textbook CGLS steps per slice in binary64, in the form ``tomo_cgls`` runs: r = b - A x, z = A^T r, p = z,
+        gam = |z|^2; per step w = A p, alpha = gam / |w|^2, x += alpha p, r -= alpha w, z = A^T r, beta = |z|^2 / gam, p = z + beta p
+        (0/0 := 0); the clamp at 0 at the end.  alpha and beta are rounded to float32, as ``k_slice_ratio`` stores them.  The slices
+        are independent: ``slices`` selects the ones to compute (of ``x0`` and ``b`` alike; ``x0 = None``: a zero start).
+        Returns (x, alpha, beta), the coefficients as (niter, nslice) arrays."""
+        b = np.asarray(b)
+        sl = np.arange(len(b)) if slices is None else np.asarray(slices)
+        b = b[sl].astype(np.float64).reshape(len(sl), self.nrow)
+        x = np.zeros((len(sl), self.N, self.N)) if x0 is None else np.array(np.asarray(x0)[sl], np.float64)
+
+        def quot(num, den):
+            return np.where(den > 0, num / np.where(den > 0, den, 1.0), 0.0).astype(np.float32).astype(np.float64)
+        r = b - self.fp(x)
+        z = self.bp(r)
+        p = z.copy()
+        gam = np.sum(z * z, axis=(1, 2))
+        alphas, betas = np.zeros((niter, len(sl))), np.zeros((niter, len(sl)))
+        for it in range(int(niter)):
+            w = self.fp(p)
+            alpha = quot(gam, np.sum(w * w, axis=1))
+            x += alpha[:, None, None] * p
+            r -= alpha[:, None] * w
+            z = self.bp(r)
+            gnew = np.sum(z * z, axis=(1, 2))
+            beta = quot(gnew, gam)
+            gam = gnew
+            p = z + beta[:, None, None] * p
+            alphas[it], betas[it] = alpha, beta
+        return np.maximum(x, 0.0), alphas, betas
+
+    def cgls_first_step(self, b):
+        """One CGLS step from x0 = 0 in binary64 with an a-priori first-order bound per element.  From zero r = b exactly (the
+        projection of a zero volume is 0), so the chain is short:
+
+        * z = A^T b under ``bp_bound``: e_z;
+        * gam = sum z^2 (float32 squares, a double sum): d_gam = ``sum(2 |z| e_z + e_z^2 + u z^2) + DSUM gam`` (the form of ``tv_gnorm``);
+        * w = A z: e_w = ``fp_bound(z)`` (the projector's own sums) + ``|A| e_z`` (it projects the device's z); den = sum w^2 likewise;
+        * alpha = gam / den, a double quotient rounded to float32: rel_alpha = d_gam / gam + d_den / den + u;
+        * x1 = alpha z (``k_slice_axpy`` onto a zero volume: a product, and a sum with 0): |alpha| e_z + |z| |alpha| rel_alpha +
+          2u |alpha z|, times ``SAFETY`` for the second-order terms; the clamp is 1-Lipschitz.
+
+        A slice with gam = 0 or den = 0 has alpha = 0 and x1 = 0 exactly (bound 0).
+        Returns (x1, bound, alpha, rel_alpha): the unrounded binary64 alpha per slice and the bound of its relative error."""
+        b = np.asarray(b, np.float64).reshape(len(b), self.nrow)
+        z, ez, _ = self.bp_bound(b)
+        az = np.abs(z)
+        gam = np.sum(z * z, axis=(1, 2))
+        dgam = np.sum(2 * az * ez + ez * ez + U * z * z, axis=(1, 2)) + DSUM(self.ncol) * gam
+        w, ew, _ = self.fp_bound(z)
+        ew = ew + self.fp(ez, absolute=True)
+        den = np.sum(w * w, axis=1)
+        dden = np.sum(2 * np.abs(w) * ew + ew * ew + U * w * w, axis=1) + DSUM(self.nrow) * den
+        ok = (gam > 0) & (den > 0)
+        alpha = np.where(ok, gam / np.where(ok, den, 1.0), 0.0)
+        rel = np.where(ok, dgam / np.where(ok, gam, 1.0) + dden / np.where(ok, den, 1.0) + U, 0.0)
+        a3 = alpha[:, None, None]
+        x1 = a3 * z
+        bound = SAFETY * (a3 * ez + az * a3 * rel[:, None, None] + 2 * U * np.abs(x1))
+        return np.maximum(x1, 0.0), bound, alpha, rel
+
+
+# ---- CGLS in float32, inputs with well separated per-slice coefficients ---------------------------------------------------------------
+def cgls_f32(fp, bp, x0, b, niter):
+    """The iteration of ``Matrix.cgls`` in float32 with double slice sums: ``fp(volume)`` / ``bp(sinogram)`` are the float32
+    oracle's projectors.  The yardstick of ``niter >= 2`` under ``seq_bound``."""
+    F = np.float32
+    b = np.asarray(b, F)
+    x = np.array(x0, F)
+
+    def quot(num, den):
+        return np.where(den > 0, num / np.where(den > 0, den, 1.0), 0.0).astype(F)
+    r = (b - fp(x)).astype(F)
+    z = bp(r)
+    p = z.copy()
+    gam = np.sum(z.astype(np.float64) ** 2, axis=(1, 2))
+    for _ in range(int(niter)):
+        w = fp(p)
+        alpha = quot(gam, np.sum(w.astype(np.float64) ** 2, axis=1))
+        x = (x + alpha[:, None, None] * p).astype(F)
+        r = (r - alpha[:, None] * w).astype(F)
+        z = bp(r)
+        gnew = np.sum(z.astype(np.float64) ** 2, axis=(1, 2))
+        beta = quot(gnew, gam)
+        gam = gnew
+        p = (z + beta[:, None, None] * p).astype(F)
+    return np.maximum(x, F(0))
+
+
+def cgls_zero_slice(nx):
+    """The slice ``cgls_sino`` leaves entirely zero: lane 1 of the float4 group in the middle of the slab."""
+    return 4 * ((nx // 2) // 4) + 1 if nx > 1 else None
+
+
+def _cgls_pattern(M, s):
+    """A smooth per-ray pattern of slice s (its frequency, phase and drift across the projections differ from slice to slice)."""
+    ray = (np.arange(M.nrow) % M.N + 0.5) / M.N
+    proj = np.arange(M.nrow) // M.N
+    return np.cos(np.pi * (1 + s % 3) * ray + 0.7 * proj + 0.37 * s)
+
+
+def cgls_sino(M, nx, seed=0, min_sep=0.02):
+    """A ``signed_sino`` plus a smooth per-ray pattern that differs per slice, slice ``cgls_zero_slice(nx)`` entirely zero.  The first
+    CGLS coefficient from a zero start, alpha_s = |A^T b_s|^2 / |A A^T b_s|^2, is scale-free, so it is the SHAPE of b_s that is
+    varied: the pattern's amplitude steps through 13 levels, and where the alpha of a slice still lies within ``min_sep``
+    (relative) of an earlier slice of its own or the previous float4 group, more of the pattern is added until it does not
+    (chosen on the CPU: ``alpha_separation`` is what the tests then assert)."""
+    b = signed_sino(nx, M.nrow, seed).astype(np.float64)
+    amp = ((np.arange(nx) * 5) % 13 + 1) * 0.35
+    for s in range(nx):
+        b[s] += amp[s] * _cgls_pattern(M, s)
+    b = b.astype(np.float32)
+    zs = cgls_zero_slice(nx)
+    if zs is not None:
+        b[zs] = 0
+
+    def alpha_of(row):
+        z = M.bp(row[None].astype(np.float64))
+        w = M.fp(z)
+        den = float(np.sum(w * w))
+        return float(np.sum(z * z)) / den if den > 0 else 0.0
+    alpha = np.zeros(nx)
+    for s in range(nx):
+        if s == zs:
+            continue
+        for k in range(1, 60):
+            alpha[s] = alpha_of(b[s])
+            near = [t for t in range(max(0, 4 * (s // 4 - 1)), s) if t != zs]
+            if all(abs(alpha[s] - alpha[t]) > min_sep * max(alpha[s], alpha[t]) for t in near):
+                break
+            b[s] = (b[s] + np.float32(0.23 * k) * _cgls_pattern(M, s + k)).astype(np.float32)
+        else:
+            raise AssertionError(f"cgls_sino: slice {s} not separated")
+    return b
+
+
+def alpha_separation(alpha, rel):
+    """The smallest ``|alpha_s - alpha_t| / max(alpha_s, alpha_t)`` over ``100 max(rel_s, rel_t)``, over every pair of slices of one
+    float4 group or of neighbouring groups (slices with alpha = 0, the zero slice, left out: any other coefficient there shows as a
+    non-zero voxel).  Above 1, a coefficient taken from a neighbour moves the step by more than 100 bounds of alpha."""
+    alpha, rel = np.asarray(alpha, np.float64), np.asarray(rel, np.float64)
+    worst = np.inf
+    for s in range(len(alpha)):
+        for t in range(max(0, 4 * (s // 4 - 1)), s):
+            if alpha[s] > 0 and alpha[t] > 0:
+                worst = min(worst, abs(alpha[s] - alpha[t]) / max(alpha[s], alpha[t]) / (100 * max(rel[s], rel[t])))
+    return worst
+
+
+def slice_sample(nx):
+    """The slices a large case is compared on: the first and the last real slice, both sides of every 64-slice boundary, and one
+    slice in each lane of a float4 group (slices 4k + lane of four different groups), ``cgls_zero_slice`` among them."""
+    s = {0, nx - 1} | {c for k in range(64, nx, 64) for c in (k - 1, k)}
+    s |= {4 * g + lane for lane, g in enumerate((1, nx // 8 + 1, nx // 5, (nx - 1) // 4 - 1))}
+    s.add(cgls_zero_slice(nx))
+    return np.array(sorted(t for t in s if t is not None and 0 <= t < nx))
+
+
+# ---- the WBP row filter (k_filter_rows) -------------------------------------------------------------------------------------------------
+def filter_rows(sino, taps, P, N):
+    """``out[p, j] = sum_k h[|j - k|] in[p, k]`` per slice and projection in binary64 (h: the float32 taps the device holds), and the
+    bound ``gamma(N + 1) sum_k |h[|j - k|]| |in[p, k]|``: N products and N sums in any order, with or without FMA contraction."""
+    h = np.asarray(taps, np.float32).astype(np.float64)
+    idx = np.abs(np.arange(N)[:, None] - np.arange(N)[None, :])
+    H = h[idx]
+    s = np.asarray(sino, np.float64).reshape(len(sino), P, N)
+    out = np.einsum("jk,spk->spj", H, s)
+    mag = np.einsum("jk,spk->spj", np.abs(H), np.abs(s))
+    return out.reshape(len(sino), P * N), (float(gamma(N + 1)) * mag).reshape(len(sino), P * N)
+
+
+# ---- the FISTA passes (k_soft_threshold, k_momentum, k_sino_extrapolate) ----------------------------------------------------------------
+def soft_threshold(v, l):
+    """``|v| > l ? copysign(|v| - l, v) : +0`` in float32: one exactly rounded subtraction, so the kernel's result bit for bit
+    (subnormals kept, -0 and |v| == l give +0)."""
+    v = np.asarray(v, np.float32)
+    l = np.float32(l)
+    a = np.abs(v)
+    return np.where(a > l, np.copysign((a - l).astype(np.float32), v), np.float32(0)).astype(np.float32)
+
+
+def momentum(r, old, beta):
+    """``y = r + beta (r - old)`` (k_momentum; beta the float32 value) in binary64 and its bound.  The kernel rounds the difference
+    (u |r - old|, carried through beta), then either the product and the sum (u |beta (r - old)| + u |y|) or, contracted to an FMA,
+    the sum alone: ``u (2 |beta (r - old)| + |y|)``, times 1.01 for the second-order terms, plus ``2 TINY`` for a difference or
+    product that underflows."""
+    beta = float(np.float32(beta))
+    r, old = np.asarray(r, np.float64), np.asarray(old, np.float64)
+    t = beta * (r - old)
+    y = r + t
+    return y, 1.01 * U * (2 * np.abs(t) + np.abs(y)) + 2 * TINY
+
+
+def sino_extrapolate(g, p_old, beta):
+    """``q = g + beta (g - p_old)`` (k_sino_extrapolate: A yk from A r and A r_old): the expression of ``momentum``, and its bound.
+    The kernel's second output, the saved A r, is a copy of g: bit for bit."""
+    return momentum(g, p_old, beta)
 
 
 # ---- TV steps (volume (nx, ny, nz), axis 0 = the slice axis) ------------------------------------------------------------------------

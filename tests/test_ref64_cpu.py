@@ -553,3 +553,234 @@ def test_oracle_lipschitz_within_bound(name, N):
     with pytest.raises(AssertionError):                               # the second largest column instead
         v = np.bincount(M.cols, M.vals * (M.rowsum * M.rowinner)[M.rows], M.ncol)
         ref64.assert_scalar("lipschitz_cimmino", np.sort(v)[-2] if np.sort(v)[-2] != v.max() else v.max() * (1 - 1e-4), L, eL)
+
+
+# ---- CGLS, the WBP row filter, the FISTA passes ----------------------------------------------------------------------------------------
+# the one-step shapes of tests/test_gpu_elementwise_misc.py (N, P, slices)
+CGLS_SHAPES = [(8, 3, 3), (9, 4, 130), (8, 3, 513), (8, 3, 1025), (33, 5, 449)]
+
+
+def _cgls_setup(N, P, nx):
+    ang = np.linspace(-70, 70, P)
+    M = ref64.Matrix(N, ang)
+    return M, ref64.cgls_sino(M, nx, seed=N + nx)
+
+
+def _sumsq_f32(v, rpb=None, drop=None, phases=1):
+    """k_slice_sumsq + _finish on (slices, rows): float32 squares summed in double.  ``drop = "last_block"``: the last (short) block of
+    ``rpb`` rows left out; ``drop = "phase"``: the 8-row groups of row phase 1 of ``phases`` left out in every block."""
+    m = v.shape[1]
+    keep = np.ones(m, bool)
+    if drop == "last_block":
+        keep[(-(-m // rpb) - 1) * rpb:] = False
+    elif drop == "phase":
+        r = np.arange(m)
+        keep[((r % rpb) // 8) % phases == 1] = False
+    sq = (v * v).astype(F32).astype(np.float64)
+    return sq[:, keep].sum(axis=1)
+
+
+def _cgls_first_f32(M, b, coef=None, drop_z=None, drop_w=None, rpb_z=None, rpb_w=None, phases=1):
+    """The first CGLS step from zero in float32 as the kernels form it; ``coef(alpha)``: the coefficient each slice is handed."""
+    orc, _ = _orc_fp(M, np.zeros((len(b), M.N, M.N), F32))
+    z = orc.back_projection(b)
+    orc.recon[:] = z
+    orc.forward_projection()
+    w = orc.g.copy()
+    gam = _sumsq_f32(z.reshape(len(b), -1), rpb_z, drop_z, phases)
+    den = _sumsq_f32(w, rpb_w, drop_w, phases)
+    alpha = np.where(den > 0, gam / np.where(den > 0, den, 1), 0).astype(F32)
+    if coef is not None:
+        alpha = coef(alpha)
+    return np.maximum((alpha[:, None, None] * z).astype(F32), F32(0))
+
+
+@pytest.mark.parametrize("N,P,nx", CGLS_SHAPES, ids=[f"N{c[0]}-nx{c[2]}" for c in CGLS_SHAPES])
+def test_cgls_inputs_separate_alpha_and_the_f32_step_is_inside_its_bound(N, P, nx):
+    M, b = _cgls_setup(N, P, nx)
+    x1, bound, alpha, rel = M.cgls_first_step(b)
+    zs = ref64.cgls_zero_slice(nx)
+    assert zs % 4 == 1 and not b[zs].any() and alpha[zs] == 0 and np.count_nonzero(alpha == 0) == 1
+    assert ref64.alpha_separation(alpha, rel) > 1.0
+    sl = ref64.slice_sample(nx)
+    assert {0, nx - 1, zs} <= set(sl.tolist()) and all(k in sl and k - 1 in sl for k in range(64, nx, 64))
+    if nx >= 8:
+        assert {int(s) % 4 for s in sl if s != zs} == {0, 1, 2, 3}            # every lane of a float4 group, the zero slice aside
+    got = _cgls_first_f32(M, b)
+    ref64.assert_within("cgls first step", got, x1, bound)
+    assert not got[zs].any() and not x1[zs].any() and not bound[zs].any()
+    # the same step through Matrix.cgls (alpha rounded to float32 there)
+    xa, al, _ = M.cgls(None, b, 1, slices=sl)
+    assert np.abs(xa - x1[sl]).max() <= 2 * ref64.U * np.abs(x1).max() and np.allclose(al[0], alpha[sl], rtol=2 * ref64.U, atol=0)
+
+
+@pytest.fixture(scope="module")
+def cgls_case():
+    M, b = _cgls_setup(9, 4, 130)
+    return (M, b) + M.cgls_first_step(b)
+
+
+@pytest.mark.parametrize("kind", ["neighbour_slice", "neighbour_group", "one_grid_stride"])
+def test_cgls_bound_catches_a_coefficient_from_the_wrong_slice(cgls_case, kind):
+    """The coefficient of slice s + 1, of the next float4 group (s + 4), and of the group an unrounded capped grid would reach on its
+    second trip ((8192 * 256) % (sx / 4) groups on, in the padded row of sx = 192 coefficients)."""
+    M, b, x1, bound, alpha, rel = cgls_case
+    nx, sx = len(b), 192
+    shift = {"neighbour_slice": 1, "neighbour_group": 4, "one_grid_stride": 4 * ((8192 * 256) % (sx // 4))}[kind]
+    assert shift % sx != 0
+
+    def coef(a):
+        pad = np.zeros(sx, F32)
+        pad[:nx] = a
+        return np.roll(pad, -shift)[:nx]
+    bad = _cgls_first_f32(M, b, coef=coef)
+    with pytest.raises(AssertionError):
+        ref64.assert_within("cgls", bad, x1, bound)
+    # ... and in every single slice on its own (the zero slice aside: any coefficient times z = 0 is 0)
+    err = (np.abs(bad - x1) > bound).reshape(nx, -1).any(axis=1)
+    zs = ref64.cgls_zero_slice(nx)
+    assert err[np.arange(nx) != zs].all()
+
+
+@pytest.mark.parametrize("kind", ["last_block_z", "last_block_w", "phase_z", "phase_w"])
+def test_cgls_bound_catches_rows_left_out_of_the_slice_sums(kind):
+    """N = 33: the pixel sum has 18 blocks of 61 rows, the last one short (52 rows); its row phases take alternate groups of 8 rows."""
+    N, P, nx = 33, 5, 6
+    M, b = _cgls_setup(N, P, nx)
+    x1, bound, _, _ = M.cgls_first_step(b)
+    mz, mw = N * N, N * P
+    rz, rw = -(-mz // ((mz + 63) // 64)), -(-mw // ((mw + 63) // 64))
+    assert (rz, mz - 17 * rz) == (61, 52)
+    ref64.assert_within("cgls", _cgls_first_f32(M, b, rpb_z=rz, rpb_w=rw, phases=2), x1, bound)
+    kw = dict(rpb_z=rz, rpb_w=rw, phases=2)
+    kw["drop_" + kind[-1]] = "last_block" if kind.startswith("last") else "phase"
+    with pytest.raises(AssertionError):
+        ref64.assert_within("cgls", _cgls_first_f32(M, b, **kw), x1, bound)
+
+
+def test_cgls_sequential_yardstick_catches_a_wrong_coefficient():
+    N, P, nx = 8, 3, 9
+    M, b = _cgls_setup(N, P, nx)
+    x0 = (F32(0.1) * ref64.dense_volume(nx, N, seed=30)).astype(F32)
+    orc, _ = _orc_fp(M, x0)
+
+    def fp(v):
+        orc.recon[:] = v
+        orc.forward_projection()
+        return orc.g.copy()
+    good = ref64.cgls_f32(fp, orc.back_projection, x0, b, 3)
+    x64, al, be = M.cgls(x0, b, 3)
+    assert al.shape == (3, nx) and be.shape == (3, nx)
+    ref64.assert_seq("cgls", good, good, x64)
+    assert np.abs(good - x64).max() <= 1e-4 * np.abs(x64).max()
+    sub, _, _ = M.cgls(x0, b, 3, slices=[2, 7])                        # the slices are independent
+    assert np.array_equal(sub, x64[[2, 7]])
+    bad = ref64.cgls_f32(fp, orc.back_projection, x0[[1, 0] + list(range(2, nx))], b, 3)   # two slices' starts exchanged
+    with pytest.raises(AssertionError):
+        ref64.assert_seq("cgls", bad, good, x64)
+    sw = ref64.cgls_f32(fp, lambda r: np.roll(orc.back_projection(r), 1, axis=0), x0, b, 3)   # every slice handed its neighbour's z
+    with pytest.raises(AssertionError):
+        ref64.assert_seq("cgls", sw, good, x64)
+
+
+def _filter_f32(b, taps, P, N, kind=None):
+    """k_filter_rows in float32 (one multiply-add per tap, k ascending).  ``kind``: "tap_plus_one" reads h[|j - k| + 1] (0 past the
+    end), "chunk0" lets the slices of the second 64-slice chunk read the first chunk's input, "next_projection" takes the last ray
+    of a projection from the next one (the element one past the row)."""
+    h = np.asarray(taps, F32)
+    s = np.asarray(b, F32).reshape(len(b), P, N)
+    if kind == "chunk0":
+        s = s.copy()
+        n2 = min(64, len(b) - 64)
+        s[64:64 + n2] = s[:n2]
+    hp = np.concatenate([h, [F32(0)]])
+    out = np.zeros_like(s)
+    for j in range(N):
+        acc = np.zeros(s.shape[:2], F32)
+        for k in range(N):
+            d = abs(j - k) + (1 if kind == "tap_plus_one" else 0)
+            col = s[:, :, k]
+            if kind == "next_projection" and k == N - 1:
+                col = np.roll(s[:, :, 0], -1, axis=1)
+            acc = (acc + (hp[d] * col).astype(F32)).astype(F32)
+        out[:, :, j] = acc
+    return out.reshape(len(b), P * N)
+
+
+def _random_taps(N, seed):
+    rng = np.random.default_rng(seed)
+    return (rng.permutation(np.geomspace(1.0, 1e-3, N)) * rng.choice([-1.0, 1.0], N)).astype(F32)
+
+
+@pytest.mark.parametrize("taps", ["ram-lak", "random"])
+def test_filter_rows_bound_holds_and_catches_wrong_indices(taps):
+    from tomo_tv_amd.engine import fbp_filter_taps
+    N, P, nx = 9, 3, 70
+    h = np.asarray(fbp_filter_taps(N, "ram-lak"), F32) if taps == "ram-lak" else _random_taps(N, 1)
+    assert taps == "ram-lak" or len(set(np.abs(h).tolist())) == N
+    b = ref64.signed_sino(nx, P * N, seed=31)
+    ref, bound = ref64.filter_rows(b, h, P, N)
+    idx = np.abs(np.arange(N)[:, None] - np.arange(N)[None, :])
+    direct = (h.astype(np.float64)[idx][None, None] * b.reshape(nx, P, 1, N).astype(np.float64)).sum(axis=3)
+    assert np.abs(direct.reshape(nx, -1) - ref).max() <= 1e-12
+    ref64.assert_within("filter", _filter_f32(b, h, P, N), ref, bound)
+    for kind in ("tap_plus_one", "chunk0", "next_projection"):
+        with pytest.raises(AssertionError):
+            ref64.assert_within("filter", _filter_f32(b, h, P, N, kind), ref, bound)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, F32).view(np.uint32)
+
+
+def _soft_inputs(l):
+    l = F32(l)
+    up, dn = np.nextafter(l, F32(4)), np.nextafter(l, F32(-1))
+    rng = np.random.default_rng(32)
+    special = np.array([l, -l, 0.0, -0.0, 1e-40, -1e-40, up, -up, dn, -dn, 2.0 ** -149, -2.0 ** -126], F32)
+    return np.concatenate([special, rng.uniform(-2, 2, 500).astype(F32)])
+
+
+@pytest.mark.parametrize("l", [0.3, 0.0])
+def test_soft_threshold_is_exact_and_catches_a_wrong_comparison_or_sign(l):
+    v = _soft_inputs(l)
+    lf = F32(l)
+    want = ref64.soft_threshold(v, l)
+    assert want.dtype == F32
+    plain = (np.sign(v) * np.maximum(np.abs(v) - lf, F32(0))).astype(F32)   # the textbook form: the same values (signs of zero apart)
+    assert np.array_equal(want, plain)
+    assert not np.signbit(want[want == 0]).any()                            # every zero is +0
+    if l == 0.0:
+        assert want[4] == v[4] != 0 and want[10] == v[10] != 0              # the subnormals survive
+    a = np.abs(v)
+    ge = np.where(a >= lf, np.copysign((a - lf).astype(F32), v), F32(0)).astype(F32)     # >= for >
+    assert np.array_equal(ge, want)                                         # equal as values ...
+    diff = _bits(ge) != _bits(want)                                         # ... the bit patterns tell: -0 at v == -l (and at -0 for l == 0)
+    assert diff.any() and np.all((a[diff] == lf) & np.signbit(v[diff]))
+    nosign = np.where(a > lf, (a - lf).astype(F32), F32(0)).astype(F32)     # the sign dropped
+    assert not np.array_equal(_bits(nosign), _bits(want)) and not np.array_equal(nosign, want)
+
+
+def _momentum_f32(r, old, beta, fma=False):
+    beta = F32(beta)
+    d = (r - old).astype(F32)
+    if fma:                                                                 # beta * d is exact in binary64: one rounding of the sum
+        return (beta.astype(np.float64) * d.astype(np.float64) + r.astype(np.float64)).astype(F32)
+    return (r + (beta * d).astype(F32)).astype(F32)
+
+
+@pytest.mark.parametrize("beta", [0.0, 0.37, 0.999])
+def test_momentum_bound_holds_and_catches_exchanged_operands(beta):
+    rng = np.random.default_rng(33)
+    r = rng.uniform(-2, 2, (5, 8, 8)).astype(F32)
+    old = (r + rng.uniform(-0.3, 0.3, r.shape)).astype(F32)
+    old[0] = r[0]                                                           # no step where nothing moved
+    for fn in (ref64.momentum, ref64.sino_extrapolate):
+        y, bound = fn(r, old, beta)
+        for fma in (False, True):
+            ref64.assert_within("momentum", _momentum_f32(r, old, beta, fma), y, bound)
+        assert np.abs(bound).max() <= 4 * ref64.U * np.abs(y).max() + 1e-30   # a few u
+        if beta == 0.0:
+            assert np.array_equal(y, r.astype(np.float64))
+        with pytest.raises(AssertionError):                                 # old and r exchanged
+            ref64.assert_within("momentum", _momentum_f32(old, r, beta), y, bound)
