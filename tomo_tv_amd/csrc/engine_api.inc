@@ -1,5 +1,5 @@
 // engine_api.inc -- part of tomo_engine.hip (ONE translation unit: the kernels are templates and asm blocks in headers; the host side is
-// split by topic into files that tomo_engine.hip includes in order).  This part: C ABI: lifetime, data in / out, projections, SIRT / SART (the resident sweep and its fail-safe) / ART / Poisson-ML / CGLS / WBP, the multimodal steps, scalars.
+// split by topic into files that tomo_engine.hip includes in order).  This part: C ABI: lifetime, data in / out, projections, SIRT / Poisson-ML / CGLS / WBP (SART and ART: engine_sart.inc), the multimodal steps, scalars.
 
 
 const char *tomo_last_error(void) { return g_err.c_str(); }
@@ -145,13 +145,6 @@ int tomo_get_dims(tomo_engine *e, int *nslice, int *nray, int *nproj, int64_t *n
     if (nray) *nray = e->n;
     if (nproj) *nproj = e->np;
     if (nnz) *nnz = e->nnz;
-    return TOMO_OK;
-}
-
-int tomo_sart_chain_count(tomo_engine *e, int *count)
-{
-    if (!e || !count) return fail(TOMO_ERR_ARG, "null");
-    *count = chain_count(e);
     return TOMO_OK;
 }
 
@@ -344,291 +337,6 @@ int tomo_sirt_data(tomo_engine *e, int vol, int sino_b, int niter)
         if ((rc = launch_bp_all(e, x, r, e->d_colsum_all, 1.f, 1.f, 1))) return rc;
     }
     return TOMO_OK;
-}
-
-// ---- the SART sweep as one launch of the volume-resident kernel (sart_resident.hip.h) ----------------------------------------------
-// Every workgroup of the launch must be on the chip at once (they wait for one another's ray sums), and a workgroup fills a CU:
-// two such launches side by side -- two engines on one device, on two streams -- could each get part of the chip and wait for the
-// rest until their spins run out.  So the resident launches of one device form a chain: each waits for the event the one before
-// it (any engine, any stream) recorded.  Other kernels may overlap freely: they finish by themselves.
-static std::mutex g_rs_mu;
-static hipEvent_t g_rs_last[64] = {};
-
-// failed: the 64-slice chunk ranges {c0, nc} the launch did not store (empty = the whole sweep is in x); the call returns after the
-// launch has finished -- one host wait per sweep (~10 us against a sweep of milliseconds) is what knowing costs
-static int launch_sart_resident(tomo_engine *e, float *x, float beta, int64_t steps, const std::function<int(int64_t)> &angle_at, float *track,
-                                std::vector<std::pair<int, int>> &failed)
-{
-    failed.clear();
-    if (steps > (int64_t)1 << 24) return fail(TOMO_ERR_ARG, "too many SART steps in one call");
-    const Chunks all = chunks64(e, whole(e));
-    const int c0 = all.c0, nc = all.n;
-    const int groups = std::max(1, std::min(e->rs_groups, nc)), rounds = (nc + groups - 1) / groups;
-    {   // the angle of every step, on the device (an unchanged sequence stays where it is)
-        std::vector<int> seq((size_t)steps);
-        for (int64_t k = 0; k < steps; ++k) seq[(size_t)k] = angle_at(k);
-        if (seq != e->rs_angs_host) {
-            HIPCHK(hipStreamSynchronize(e->stream));          // (a sweep in flight may still read the old sequence; rare: the first sweep, a new order)
-            if ((size_t)steps > e->rs_angs_cap) {
-                if (e->d_rs_angs) { e->pool.release(e->d_rs_angs); e->rs_angs_cap = 0; }
-                if (int rc = dev_alloc(e, GEOMETRY, (void **)&e->d_rs_angs, (size_t)steps * sizeof(int), false)) return rc;
-                e->rs_angs_cap = (size_t)steps;
-            }
-            HIPCHK(hipMemcpy(e->d_rs_angs, seq.data(), (size_t)steps * sizeof(int), hipMemcpyHostToDevice));
-            e->rs_angs_host.swap(seq);
-        }
-    }
-    const uint64_t need = (uint64_t)rounds * (uint64_t)steps;
-    if ((uint64_t)e->rs_epoch + need + 16 > 0xFFFFFFFFull) {     // the tags wrap: back to the state after creation (tag 0 = never written)
-        HIPCHK(hipMemsetAsync(e->rs_pb, 0, e->rs_pb_bytes, e->stream));
-        HIPCHK(hipMemsetAsync(e->rs_rb, 0, e->rs_rb_bytes, e->stream));
-        e->rs_epoch = 0;
-    }
-    // commit words: all at rs_commit_base (every launch covers every chunk and adds the number of tiles to each word when it commits);
-    // cleared after a launch that did not commit, and before the count could reach the poison bit
-    if (c0 != 0 || nc != e->sxc / 64) return fail(TOMO_ERR_STATE, "the resident sweep covers the whole slab");
-    if (e->rs_commit_dirty || e->rs_commit_base > 0x7F000000u) {
-        HIPCHK(hipMemsetAsync(e->d_rs_commit, 0, (size_t)(e->sxc / 64) * sizeof(unsigned), e->stream));
-        e->rs_commit_base = 0; e->rs_commit_dirty = false;
-    }
-    if (++e->rs_seq >= 0x7FFFFFF0u) { std::memset(e->rs_done, 0, (size_t)(e->sxc / 64) * sizeof(int)); e->rs_seq = 1; }
-    RsArgs A{};
-    A.x = x; A.b = e->cur_b; A.rowsum = e->d_rowsum; A.hdr = e->d_rs_hdr; A.cell = e->d_rs_cell; A.ts = e->d_rs_ts; A.rl = e->d_rs_rl;
-    A.pb = e->rs_pb; A.rb = e->rs_rb; A.angs = e->d_rs_angs; A.track = track; A.part = e->d_part; A.abort_word = e->d_rs_abort; A.abort_host = e->rs_abort;
-    A.commit = e->d_rs_commit; A.done_host = e->rs_done; A.seq = e->rs_seq; A.commit_base = e->rs_commit_base; A.test_fail = e->rs_test_fail;
-    A.n = e->n; A.sx = e->sx; A.np = e->np; A.ntiles = e->rs_ntiles; A.tiles = e->rs_tiles; A.rpt = e->rs_rpt; A.steps = (int)steps; A.chunk0 = c0; A.nchunk = nc;
-    A.epoch0 = e->rs_epoch; A.spin_limit = e->rs_spin_limit; A.beta = beta; A.prof = nullptr;
-    e->rs_epoch += (uint32_t)need;
-    if (e->device < 0 || e->device >= 64) return fail(TOMO_ERR_ARG, "device index");
-    {
-        std::lock_guard<std::mutex> lk(g_rs_mu);
-        hipEvent_t &last = g_rs_last[e->device];
-        if (!last) HIPCHK(hipEventCreateWithFlags(&last, hipEventDisableTiming));
-        else HIPCHK(hipStreamWaitEvent(e->stream, last, 0));
-        {
-            ProfScope ps(e, TOMO_K_SART_RESIDENT);
-            hipLaunchKernelGGL(k_sart_resident, dim3((unsigned)(e->rs_ntiles * groups)), dim3(RS_THREADS), 0, e->stream, A);
-            LAUNCHCHK();
-        }
-        HIPCHK(hipEventRecord(last, e->stream));
-    }
-    // the verdict: which chunks carry this launch's sequence number
-    HIPCHK(hipStreamSynchronize(e->stream));
-    int nfailed = 0;
-    for (int c = c0; c < c0 + nc; ++c) {
-        if (e->rs_done[c] == (int)e->rs_seq) continue;
-        ++nfailed;
-        if (!failed.empty() && failed.back().first + failed.back().second == c) ++failed.back().second;
-        else failed.emplace_back(c, 1);
-    }
-    if (nfailed) {
-        e->rs_commit_dirty = true;
-        e->rs_last_code = *e->rs_abort;
-        *e->rs_abort = 0;
-        HIPCHK(hipMemsetAsync(e->d_rs_abort, 0, sizeof(int), e->stream));
-        ++e->rs_fallbacks;
-        e->rs_fallback_chunks += nfailed;
-        e->rs_backoff = std::min(64, std::max(1, 2 * e->rs_backoff));
-        e->rs_skip = e->rs_backoff;
-    } else {
-        e->rs_commit_base += (unsigned)e->rs_ntiles;
-        e->rs_backoff = 0;
-    }
-    return TOMO_OK;
-}
-
-int tomo_sart(tomo_engine *e, int vol, float beta, int niter, const int32_t *order)
-{
-    return tomo_sart_data(e, vol, TOMO_SINO_B, beta, niter, order);
-}
-
-// track_vol >= 0: the last back-projection of the sweep also leaves ||x_new - track||^2 in scalar `slot` and copies x_new
-// into track_vol (tomo_sart_tracked)
-static int sart_impl(tomo_engine *e, int vol, int sino_b, float beta, int niter, const int32_t *order, int track_vol, int slot)
-{
-    NEED(e);
-    float *x, *r, *track = nullptr; int rc;
-    if ((rc = get_vol(e, vol, &x)) || (rc = get_sino(e, &e->sino[TOMO_SINO_R], &r)) || (rc = sino_slot(e, sino_b, &e->cur_b))) return rc;
-    if (track_vol >= 0) {
-        if (track_vol == vol) return fail(TOMO_ERR_ARG, "the tracked volume must differ from the swept one");
-        if (slot < 0 || slot >= TOMO_S_COUNT) return fail(TOMO_ERR_ARG, "bad scalar slot");
-        if ((rc = get_vol(e, track_vol, &track))) return rc;
-        if ((int64_t)niter * e->np <= 0) {   // nothing is swept: the plain pair of passes
-            if ((rc = tomo_diff_norm_sq(e, vol, track_vol, slot))) return rc;
-            return tomo_copy_volume(e, track_vol, vol);
-        }
-        if ((rc = reduce_begin(e))) return rc;
-    }
-    auto finish = [&]() -> int { return track ? reduce_end(e, slot) : TOMO_OK; };
-    if (order) {
-        std::vector<char> seen(e->np, 0);
-        for (int q = 0; q < e->np; ++q) {
-            if (order[q] < 0 || order[q] >= e->np || seen[order[q]]) return fail(TOMO_ERR_ARG, "SART order is not a permutation of the angles");
-            seen[order[q]] = 1;
-        }
-    }
-    const int64_t steps = (int64_t)niter * e->np;
-    auto angle_at = [&](int64_t k) { int q = (int)(k % e->np); return order ? order[q] : q; };
-    if (!e->sart_fused) {
-        // reference structure: one forward projection + one back-projection update per angle
-        for (int64_t k = 0; k < steps; ++k) {
-            int i = angle_at(k);
-            {
-                ProfScope ps(e, TOMO_K_FP_ANGLE);
-                if ((rc = launch_fp<FP_RESID_NORM>(e, x, i * e->n, e->n, e->cur_b, r))) return rc;
-            }
-            if ((rc = launch_bp_angle(e, x, i, r + (size_t)i * e->n * e->sx, beta, k == steps - 1 ? track : nullptr))) return rc;
-        }
-        return finish();
-    }
-    // fused chain: FP(a0) ; [BP(a_k) + FP(a_k+1)] for every consecutive pair ; BP(a_last)
-    if (steps <= 0) return TOMO_OK;
-    int form = select_forms(e).sart;
-    if (form == TOMO_FORM_SART_RESIDENT && e->rs_skip > 0 && e->sart_resident != 1) {   // sitting out after a sweep that could not finish
-        --e->rs_skip;
-        form = TOMO_FORM_SART_TILE;
-    }
-    // the streamed tile form, in place: over the whole slab (as one chain or several), or over the chunk ranges a resident launch left
-    auto sweep_tiles = [&](const std::vector<std::pair<int, int>> *ranges) -> int {
-        // cooperative chain (k_sart_tile COOP): needs consecutive angles to differ (np >= 2) and whole 64-slice chunks
-        const bool coop = e->sart_coop && e->np >= 2 && steps >= 2 && !ranges;
-        int rc2;
-        if ((rc2 = sart_tile_prepare(e, coop))) return rc2;
-        const uint32_t epoch0 = e->st_epoch + 1;             // link k publishes with epoch0 + k (both sub-slab chains alike)
-        if (coop) e->st_epoch += (uint32_t)(steps + 1);
-        // link k of the chain: 0 = FP(a0); 1..steps-1 = BP(a_k-1) + FP(a_k); steps = BP(a_last)
-        auto link = [&](int64_t k, const Sub &sb) -> int {
-            int rc3;
-            if (coop) {
-                float *pk = (k & 1) ? e->st_partial2 : e->st_partial, *pk1 = (k & 1) ? e->st_partial : e->st_partial2;   // P[k&1], P[(k-1)&1]
-                if (k == 0) return launch_sart_tile<false>(e, sb, x, 0, angle_at(0), r, beta, pk, false);
-                if (k == steps) {
-                    int last = angle_at(steps - 1);
-                    if ((rc3 = launch_resid_finish_tile(e, sb, pk1, last, r))) return rc3;
-                    return launch_bp_angle(e, sb, x, last, r + (size_t)last * e->n * e->sx, beta, track);
-                }
-                return launch_sart_coop(e, sb, x, angle_at(k - 1), angle_at(k), r, beta, pk1, pk, epoch0 + (uint32_t)k, k);
-            }
-            if (k == 0) return launch_sart_tile<false>(e, sb, x, 0, angle_at(0), r, beta);
-            if (k == steps) { int last = angle_at(steps - 1); return launch_bp_angle(e, sb, x, last, r + (size_t)last * e->n * e->sx, beta, track); }
-            int prev = angle_at(k - 1), next = angle_at(k);
-            if (prev == next) {
-                if ((rc3 = launch_bp_angle(e, sb, x, prev, r + (size_t)prev * e->n * e->sx, beta))) return rc3;
-                return launch_sart_tile<false>(e, sb, x, 0, next, r, beta);
-            }
-            return launch_sart_tile<true>(e, sb, x, prev, next, r, beta, nullptr, true, k);
-        };
-        auto chain = [&](const Sub &sb) -> int {
-            for (int64_t k = 0; k <= steps; ++k) { int rc3 = link(k, sb); if (rc3) return rc3; }
-            return TOMO_OK;
-        };
-        if (!ranges) return run_chains(e, chain);
-        for (const auto &rg : *ranges) {     // one after the other on the engine's stream (they share the partial-sum buffer)
-            const int c0 = rg.first, nc = rg.second;
-            const int vec = (c0 % 4 == 0 && nc % 4 == 0) ? 4 : (c0 % 2 == 0 && nc % 2 == 0) ? 2 : 1;
-            if ((rc2 = chain(Sub{e->stream, c0, nc, vec}))) return rc2;
-        }
-        return TOMO_OK;
-    };
-    if (form == TOMO_FORM_SART_RESIDENT) {      // the volume-resident sweep: one launch, the slab read and written once
-        std::vector<std::pair<int, int>> failed;
-        if ((rc = launch_sart_resident(e, x, beta, steps, angle_at, track, failed))) return rc;
-        // chunks whose workgroups could not all finish (the device was shared) were not stored: the streamed chain sweeps them
-        if (!failed.empty() && (rc = sweep_tiles(&failed))) return rc;
-        return finish();
-    }
-    if (e->sart_resident == 1 && !e->rs_ok) return fail(TOMO_ERR_STATE, "\"sart_resident\" = 1, but this engine has no tables of the resident sweep (N not a multiple of 8, more 32 x 32 tiles than CUs, or a matrix whose ray windows do not fit)");
-    if (form == TOMO_FORM_SART_TILE) {   // tile form, in place
-        if ((rc = sweep_tiles(nullptr))) return rc;
-        return finish();
-    }
-    float *alt;
-    if ((rc = ensure_seg_tables(e))) return rc;           // the ray-walk form's tables (built at creation only where it is the expected form)
-    if ((rc = get_scratch(e, &e->sart_alt, &alt))) return rc;
-    float *cur = x;
-    if ((rc = launch_sart_seg<false>(e, cur, nullptr, 0, angle_at(0), r, beta))) return rc;
-    for (int64_t k = 1; k < steps; ++k) {
-        int prev = angle_at(k - 1), next = angle_at(k);
-        if (prev == next) {   // single-angle geometry: the residual rows read and written would be the same
-            if ((rc = launch_bp_angle(e, cur, prev, r + (size_t)prev * e->n * e->sx, beta))) return rc;
-            if ((rc = launch_fp<FP_RESID_NORM>(e, cur, next * e->n, e->n, e->cur_b, r))) return rc;
-            continue;
-        }
-        if ((rc = launch_sart_seg<true>(e, cur, alt, prev, next, r, beta))) return rc;
-        std::swap(cur, alt);
-    }
-    int last = angle_at(steps - 1);
-    if ((rc = launch_bp_angle(e, cur, last, r + (size_t)last * e->n * e->sx, beta, track))) return rc;
-    if (cur != x) { e->vol[vol] = cur; e->sart_alt = x; }   // the swept volume now lives in the partner buffer
-    return finish();
-}
-
-int tomo_sart_data(tomo_engine *e, int vol, int sino_b, float beta, int niter, const int32_t *order)
-{
-    return sart_impl(e, vol, sino_b, beta, niter, order, -1, 0);
-}
-
-int tomo_sart_tracked(tomo_engine *e, int vol, int sino_b, float beta, int niter, const int32_t *order, int track_vol, int slot)
-{
-    return sart_impl(e, vol, sino_b, beta, niter, order, track_vol, slot);
-}
-
-int tomo_art(tomo_engine *e, float beta) { return tomo_art_order(e, beta, nullptr); }
-
-int tomo_art_order(tomo_engine *e, float beta, const int32_t *order_host)
-{
-    NEED(e);
-    float *x;
-    { int rc_ = get_vol(e, TOMO_VOL_RECON, &x); if (rc_) return rc_; }
-    int32_t *d_order = nullptr;
-    if (order_host) {
-        std::vector<char> seen(e->nrows, 0);
-        for (int64_t q = 0; q < e->nrows; ++q) {
-            if (order_host[q] < 0 || order_host[q] >= e->nrows || seen[order_host[q]]) return fail(TOMO_ERR_ARG, "row order is not a permutation");
-            seen[order_host[q]] = 1;
-        }
-        int rc = ensure_stage(e, e->nrows * sizeof(int32_t)); if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(e->stage, order_host, e->nrows * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-        d_order = (int32_t *)e->stage;
-    }
-    if (!order_host && e->art_chain && e->art_chain_ok) {
-        // natural order: one angle = forward projection + recurrence along the rays + back-projection (k_art_chain)
-        float *d, *a; int rc;
-        if ((rc = get_sino(e, &e->sino[TOMO_SINO_G], &d)) || (rc = get_sino(e, &e->sino[TOMO_SINO_R], &a))) return rc;
-        const float *b = e->sino[TOMO_SINO_B];
-        if (e->art_tile && e->sart_tile && e->st_ok && e->np >= 1) {
-            // the same fused steps as the SART sweep: FP(a0); [BP_art(a_k-1) + FP(a_k)] ...; BP_art(a_last), the residual rows of
-            // each angle formed by k_art_chain from the tile step's row sums.  Per angle 228 instead of 323 us at 512^3.
-            if ((rc = sart_tile_prepare(e, false))) return rc;
-            e->cur_b = const_cast<float *>(b);
-            const int np = e->np;
-            auto chain = [&](const Sub &sb) -> int {        // one sub-slab's (or the whole slab's) chain of launches
-                const Chunks ch = chunks64(e, sb);
-                for (int i = 0; i < np; ++i) {
-                    int rc2 = i == 0 ? launch_sart_tile<false, true>(e, sb, x, 0, 0, a, beta, nullptr, true, -1, d)
-                                     : launch_sart_tile<true, true>(e, sb, x, i - 1, i, a, beta, nullptr, true, i, d);
-                    if (rc2) return rc2;
-                    hipLaunchKernelGGL(k_art_chain, dim3((unsigned)ch.n), dim3(64 * ART_CW), 0, sb.stream, d, b, e->d_rowinner, e->d_rowcross, a, beta, i * e->n, e->n, e->sx, ch.c0);
-                    LAUNCHCHK();
-                }
-                return launch_bp_art(e, sb, x, np - 1, a, beta);
-            };
-            if ((rc = run_chains(e, chain))) return rc;
-            return tomo_positivity(e, TOMO_VOL_RECON);
-        }
-        for (int i = 0; i < e->np; ++i) {
-            if ((rc = launch_fp<FP_STORE>(e, x, i * e->n, e->n, nullptr, d))) return rc;
-            hipLaunchKernelGGL(k_art_chain, dim3((unsigned)(e->sx / 64)), dim3(64 * ART_CW), 0, e->stream, d, b, e->d_rowinner, e->d_rowcross, a, beta, i * e->n, e->n, e->sx, 0);
-            LAUNCHCHK();
-            if ((rc = launch_bp_art(e, whole(e), x, i, a, beta))) return rc;
-        }
-        return tomo_positivity(e, TOMO_VOL_RECON);
-    }
-    hipLaunchKernelGGL(k_art, dim3(e->sxc / 64), dim3(64 * ART_WAVES), 0, e->stream, x, e->d_rptr, e->d_rent, e->sino[TOMO_SINO_B], e->d_rowinner, beta, (int)e->nrows, e->sx, d_order);
-    LAUNCHCHK();
-    int rc = tomo_positivity(e, TOMO_VOL_RECON);
-    if (!rc && order_host) HIPCHK(hipStreamSynchronize(e->stream));   // the staging buffer holds the order until the sweep is done
-    return rc;
 }
 
 int tomo_poisson_ml(tomo_engine *e, float lambda)

@@ -1,5 +1,5 @@
 // engine_create.inc -- part of tomo_engine.hip (ONE translation unit: the kernels are templates and asm blocks in headers; the host side is
-// split by topic into files that tomo_engine.hip includes in order).  This part: creation: host tables -> device (finish_create_impl), teardown on failure, the launch chains of a sweep (run_chains).
+// split by topic into files that tomo_engine.hip includes in order).  This part: creation: host tables -> device (finish_create_impl), teardown on failure.
 
 // ---- creation ----------------------------------------------------------------------------------------------
 // host tables are released as soon as they are on the device (peak host memory: a few times nnz * 8 bytes per engine,
@@ -197,7 +197,7 @@ static int finish_create_impl(tomo_engine *e, Coo &m, tomo_engine **out)
                     if ((rc = dev_alloc(e, GEOMETRY, (void **)&e->d_rs_abort, sizeof(int), true)) || (rc = dev_alloc(e, GEOMETRY, (void **)&e->d_rs_commit, (size_t)(e->sxc / 64) * sizeof(unsigned), true))) return rc;
                     if (!e->rs_done) { HIPCHK(hipHostMalloc((void **)&e->rs_done, (size_t)(e->sxc / 64) * sizeof(int), hipHostMallocMapped)); }
                     std::memset(e->rs_done, 0, (size_t)(e->sxc / 64) * sizeof(int));
-                    e->rs_epoch = 0; e->rs_seq = 0; e->rs_commit_base = 0; e->rs_commit_dirty = false;
+                    e->rs.epoch = 0; e->rs.seq = 0; e->rs.commit_base = 0; e->rs.commit_dirty = false;
                     e->rs_ok = true;
                 }
             }
@@ -263,7 +263,7 @@ static tomo_engine *new_engine(int nslice, int nray, int nproj, int device)
     e->vec = (e->sxc % 256 == 0) ? 4 : (e->sxc % 128 == 0) ? 2 : 1;
     // Row pitch = computed width.  A pixel's row of slices that is a multiple of 4 KB (1024 slices) makes two sweep chains striding over
     // alternate halves of the rows alias the memory channels (round 2: 51.3 against 40.6 ms per sweep at 1024 slices), so such a slab
-    // runs ONE chain (chain_count).  Round 4 measured 64 slices of padding on the pitch so that it can run two: 1024^3 x 120 ASD-POCS
+    // runs ONE chain (chain_count, engine_sart.inc).  Round 4 measured 64 slices of padding on the pitch so that it can run two: 1024^3 x 120 ASD-POCS
     // step 208.7 ms against 206.6 ms with one chain on the plain pitch -- no gain; the environment hook of that experiment is gone
     // (round 5, ADVICE r4: several launches size their work from the pitch, so a padded pitch was not safe to ship).
     e->sx = e->sxc;
@@ -277,64 +277,4 @@ static int check_dims(int nslice, int nray, int nproj)
     if (nslice <= 0 || nray <= 0 || nproj <= 0) return fail(TOMO_ERR_ARG, "Nslice, Nray and Nproj must be positive");
     if (nray > 4096) return fail(TOMO_ERR_ARG, "Nray > 4096 not supported (float32 index storage limit of parallelRay)");
     return TOMO_OK;
-}
-
-// A sweep over a slab as one chain of launches on the engine's stream, or as two chains over two sub-slabs (64-slice chunks,
-// equal halves) on two streams: slices are independent, and each stream's short kernels and launch boundaries disappear under
-// the other stream's tile step.  A sweep is then 2 x ~180 launches of ~100 us kernels: one host thread cannot enqueue both chains
-// fast enough to keep both streams fed (measured: 19.4 ms per sweep against 19.9 on one stream), so the second chain is enqueued
-// by a second host thread (18.0 ms: what two independent engines on two Python threads reach).
-// "sart_streams": 2 = always (when the slab has two chunks), 1 = never, 0 = auto: equal halves, and not when a pixel's row of
-// slices is a multiple of 4 KB -- the two halves of such rows land on the same memory channels (1024 slices: 48.5 against 42.9 ms
-// per ASD-POCS step; 128 / 256 / 512 / 768 slices: -2.6 / -3.3 / -5.5 / -5.3 %).
-// chains a sweep of this engine's slab runs as, under the current "sart_streams" (also what tomo_sart_chain_count reports)
-static int chain_count(const tomo_engine *e)
-{
-    const int units = e->sxc / 64;
-    const bool two = e->sart_streams >= 2 || (e->sart_streams == 0 && units % 2 == 0 && (e->sx * sizeof(float)) % 4096 != 0);
-    if (!(two && units >= 2)) return 1;
-    if (e->sart_streams > 2) return std::min(std::min(e->sart_streams, (int)tomo_engine::MAX_CHAINS), units);
-    return 2;   // "sart_streams" = 3 / 4: that many chains (measured at 512 slices: 2 chains 22.4 ms per step, 3: 24.1, 4: 22.7)
-}
-
-template <class Chain>
-static int run_chains(tomo_engine *e, const Chain &chain)
-{
-    const int units = e->sxc / 64;                       // 64-slice chunks; a sub-slab's per-row kernels use the widest vector that fits
-    auto vec_of = [](int c0, int nc) { return (c0 % 4 == 0 && nc % 4 == 0) ? 4 : (c0 % 2 == 0 && nc % 2 == 0) ? 2 : 1; };
-    const int nch = chain_count(e);
-    if (nch < 2) return chain(whole(e));
-    if (!e->ev_sfork) HIPCHK(hipEventCreateWithFlags(&e->ev_sfork, hipEventDisableTiming));
-    for (int u = 0; u < nch; ++u)
-        if (!e->sub_stream[u]) {
-            HIPCHK(hipStreamCreateWithFlags(&e->sub_stream[u], hipStreamNonBlocking));
-            HIPCHK(hipEventCreateWithFlags(&e->ev_sjoin[u], hipEventDisableTiming));
-        }
-    HIPCHK(hipEventRecord(e->ev_sfork, e->stream));
-    Sub sbs[tomo_engine::MAX_CHAINS];
-    for (int u = 0, c0 = 0; u < nch; ++u) {
-        const int nc = units / nch + (u < units % nch ? 1 : 0);
-        sbs[u] = Sub{e->sub_stream[u], c0, nc, vec_of(c0, nc)};
-        c0 += nc;
-    }
-    for (int u = 0; u < nch; ++u) HIPCHK(hipStreamWaitEvent(e->sub_stream[u], e->ev_sfork, 0));
-    int rcs[tomo_engine::MAX_CHAINS] = {TOMO_OK, TOMO_OK, TOMO_OK, TOMO_OK};
-    std::string errs[tomo_engine::MAX_CHAINS];
-    for (int u = 1; u < nch; ++u) {                        // chains 1.. are enqueued by the engine's persistent helper threads
-        if (!e->chain_helper[u]) {
-            e->chain_helper[u].reset(new ChainHelper());
-            e->chain_helper[u]->start(e->device);
-        }
-        e->chain_helper[u]->submit([&, u]() {
-            rcs[u] = chain(sbs[u]);
-            if (rcs[u]) errs[u] = g_err;                  // the error text is thread-local
-        });
-    }
-    rcs[0] = chain(sbs[0]);
-    for (int u = 1; u < nch; ++u) e->chain_helper[u]->wait();
-    for (int u = 1; u < nch; ++u) if (rcs[u] && !rcs[0]) { rcs[0] = rcs[u]; g_err = errs[u]; }
-    for (int u = 0; u < nch; ++u)
-        if (hipEventRecord(e->ev_sjoin[u], e->sub_stream[u]) != hipSuccess && !rcs[0]) rcs[0] = fail(TOMO_ERR_HIP, "hipEventRecord(sub-slab join)");
-    for (int u = 0; u < nch; ++u) HIPCHK(hipStreamWaitEvent(e->stream, e->ev_sjoin[u], 0));
-    return rcs[0];
 }

@@ -1,6 +1,6 @@
 // engine_launch.inc -- part of tomo_engine.hip (ONE translation unit: the kernels are templates and asm blocks in headers; the host side is
-// split by topic into files that tomo_engine.hip includes in order).  This part: which kernel family runs (select_forms) and the launch
-// helpers of the projectors, the SART steps and the all-angle back projection.  The forward projectors take the Lane they run on; the three
+// split by topic into files that tomo_engine.hip includes in order).  This part: which kernel family runs (select_forms, select_sart) and the
+// launch helpers of the projectors (the steps of a SART sweep are in engine_sart.inc).  The forward projectors take the Lane they run on; the three
 // partial-sum families of the all-angle one (tile, strip, list) differ in their main kernel only and share one pass loop (fp_passes).
 
 // ---- run-time value -> template argument ----------------------------------------------------------------------
@@ -174,21 +174,38 @@ static int launch_fp_list(tomo_engine *e, const Lane &ln, const float *x, const 
 //                                  ROWS   ray-driven k_fp_rows / k_fp_rows_g: "fp_tile" = 0 only
 //   all-angle back projection      LIST   k_bp_list: whole 128-slice pieces, P <= 192;  TILE  k_bp_tile: other slabs, P <= FB_MAX_PROJ;
 //                                  ALL    voxel-driven k_bp_all: the fallback
-//   SART sweep                     RESIDENT  k_sart_resident: N a multiple of 8, one 32 x 32 tile per CU, ray windows fit (resident.cpp)
+//   SART sweep (select_sart)       RESIDENT  k_sart_resident: N a multiple of 8, one 32 x 32 tile per CU, ray windows fit (resident.cpp);
+//                                            after a launch that could not finish it sits out some sweeps, which run as TILE
 //                                  TILE      k_sart_tile chain + k_resid_finish: N = 1024, fallbacks, "sart_resident" = 0
-//                                  ANGLE     one FP + one BP launch per angle: "sart_fused" = 0 or no tile tables
+//                                  SEG       ray-walk k_sart_seg + k_resid_finish, the volume in a ping-pong pair: no tile tables or
+//                                            "sart_tile" = 0 (reported as ANGLE: the public codes name three families)
+//                                  ANGLE     one FP + one BP launch per angle: "sart_fused" = 0
+enum SartForm { SART_ANGLE, SART_SEG, SART_TILE, SART_RESIDENT };
+// form: what the next sweep runs;  sits_out: ... TILE in place of RESIDENT, and that sweep uses up one of the sit-outs (rs.skip);
+// no_tables: "sart_resident" = 1 insists on tables this engine does not have: the sweep is an error, raised before any launch
+struct SartChoice { SartForm form; bool sits_out, no_tables; };
+static SartChoice select_sart(const tomo_engine *e)
+{
+    if (!e->sart_fused) return {SART_ANGLE, false, false};
+    if (e->sart_resident != 0 && e->rs_ok) {          // (the resident tables exist only where the tile tables do)
+        const bool sits_out = e->rs.skip > 0 && e->sart_resident != 1;
+        return {sits_out ? SART_TILE : SART_RESIDENT, sits_out, false};
+    }
+    return {(e->sart_tile && e->st_ok) ? SART_TILE : SART_SEG, false, e->sart_resident == 1};
+}
+
 struct Forms { int fp, bp, sart; };
 static Forms select_forms(const tomo_engine *e)
 {
     Forms f;
+    const SartChoice s = select_sart(e);
     f.fp = (e->fp_strip && e->fp_list && e->fl_ok && e->sxc % 128 == 0) ? TOMO_FORM_FP_LIST
          : (e->fp_strip && e->fs_ok) ? TOMO_FORM_FP_STRIP
          : e->fp_tile ? TOMO_FORM_FP_TILE : TOMO_FORM_FP_ROWS;
     f.bp = (e->bp_tile && e->bl_ok && e->bp_list && e->sxc % 128 == 0) ? TOMO_FORM_BP_LIST
          : (e->bp_tile && e->fb_ok) ? TOMO_FORM_BP_TILE : TOMO_FORM_BP_ALL;
-    f.sart = !e->sart_fused ? TOMO_FORM_SART_ANGLE
-           : (e->sart_resident != 0 && e->rs_ok) ? TOMO_FORM_SART_RESIDENT
-           : (e->sart_tile && e->st_ok) ? TOMO_FORM_SART_TILE : TOMO_FORM_SART_ANGLE;
+    f.sart = (s.form == SART_RESIDENT || s.sits_out) ? TOMO_FORM_SART_RESIDENT      // (the family the engine is set to, sitting out or not)
+           : s.form == SART_TILE ? TOMO_FORM_SART_TILE : TOMO_FORM_SART_ANGLE;
     return f;
 }
 
@@ -230,7 +247,8 @@ static bool slab_streams(const tomo_engine *e)
 
 constexpr int BP_PPW = 4;
 
-static int launch_bp_angle(tomo_engine *e, const Sub &sb, float *x, int angle, const float *r_angle, float beta, float *track = nullptr)
+// the SART update of angle `angle` from its rows of the residual sinogram r (k_bp_angle)
+static int launch_bp_angle(tomo_engine *e, const Sub &sb, float *x, int angle, const float *r, float beta, float *track = nullptr)
 {
     ProfScope ps(e, TOMO_K_BP_ANGLE, sb.stream);
     const int vec = sub_vec(e, sb);              // (a sub-slab is whole multiples of 64*vec slices)
@@ -239,165 +257,9 @@ static int launch_bp_angle(tomo_engine *e, const Sub &sb, float *x, int angle, c
     dim3 grid((unsigned)(((int64_t)ngroups * nchunk + 3) / 4)), block(256);
     double *part = track ? e->d_part : nullptr;  // tracked: the caller brackets with reduce_begin / reduce_end
     with_vec(vec, [&](auto V) { with_flag(track != nullptr, [&](auto T) {
-        hipLaunchKernelGGL((k_bp_angle<V(), BP_PPW, T()>), grid, block, 0, sb.stream, x, e->d_cell + (size_t)angle * e->npix, r_angle, beta, (int)e->npix, e->sx,
+        hipLaunchKernelGGL((k_bp_angle<V(), BP_PPW, T()>), grid, block, 0, sb.stream, x, e->d_cell + (size_t)angle * e->npix, r + (size_t)angle * e->n * e->sx, beta, (int)e->npix, e->sx,
                            ngroups, nchunk, track, part, ch.c0 / vec);
     }); });
-    LAUNCHCHK();
-    return TOMO_OK;
-}
-
-static int launch_bp_angle(tomo_engine *e, float *x, int angle, const float *r_angle, float beta, float *track = nullptr)
-{
-    return launch_bp_angle(e, whole(e), x, angle, r_angle, beta, track);
-}
-
-// the chained ART's back projection of angle `angle` (k_bp_art); a = the rows k_art_chain left, all angles
-static int launch_bp_art(tomo_engine *e, const Sub &sb, float *x, int angle, const float *a, float beta)
-{
-    const int vec = sub_vec(e, sb);
-    const Chunks ch = chunks64(e, sb);
-    const int nchunk = ch.n / vec, ngroups = (int)((e->npix + BP_PPW - 1) / BP_PPW);
-    dim3 grid((unsigned)(((int64_t)ngroups * nchunk + 3) / 4));
-    with_vec(vec, [&](auto V) {
-        hipLaunchKernelGGL((k_bp_art<V(), BP_PPW>), grid, dim3(256), 0, sb.stream, x, e->d_cell + (size_t)angle * e->npix, a + (size_t)angle * e->n * e->sx, beta,
-                           (int)e->npix, e->sx, ngroups, nchunk, slab_streams(e) ? 1 : 0, ch.c0 / vec);
-    });
-    LAUNCHCHK();
-    return TOMO_OK;
-}
-
-// segmented per-angle step: FUSED -> BP(prev) + FP(next); else plain FP(next).  Leaves the residual rows of `next` in r.
-template <bool FUSED>
-static int launch_sart_seg(tomo_engine *e, const float *x_old, float *x_new, int prev, int next, float *r, float beta)
-{
-    int rc;
-    if (!e->seg_partial) {
-        if ((rc = dev_alloc(e, GEOMETRY, (void **)&e->seg_partial, (size_t)std::max<uint32_t>(1, e->max_items) * e->sx * sizeof(float), true))) return rc;
-    }
-    int nchunk = e->sxc / (64 * e->vec);
-    uint32_t b0 = e->h_seg_exec_ptr[next], b1 = e->h_seg_exec_ptr[next + 1];
-    int L = (int)((b1 - b0) / 8);
-    const SegItemD *exec = e->d_seg_exec + b0;
-    const CellD *cell = FUSED ? e->d_cell + (size_t)prev * e->npix : nullptr;
-    const float *rp = FUSED ? r + (size_t)prev * e->n * e->sx : nullptr;
-    if (L > 0) {
-        ProfScope ps(e, FUSED ? TOMO_K_SART_FUSED : TOMO_K_FP_ANGLE);
-        dim3 grid((unsigned)(8 * (int64_t)L * nchunk)), block(64);
-        with_vec(e->vec, [&](auto V) {
-            hipLaunchKernelGGL((k_sart_seg<V(), 8, FUSED>), grid, block, 0, e->stream, x_old, x_new, exec, L, e->d_went, cell, rp, beta, e->seg_partial, e->sx);
-        });
-        LAUNCHCHK();
-    }
-    {
-        dim3 grid((unsigned)((int64_t)e->n * nchunk)), block(256);
-        with_vec(e->vec, [&](auto V) {
-            hipLaunchKernelGGL((k_resid_finish<V()>), grid, block, 0, e->stream, e->seg_partial, e->d_row_first, e->d_row_nseg, e->cur_b, e->d_rowsum, r, next * e->n, e->n, nchunk, e->sx, 0);
-        });
-        LAUNCHCHK();
-    }
-    return TOMO_OK;
-}
-
-// tile form of the per-angle step (k_sart_tile): FUSED -> BP(prev) + FP(next), in place; else plain FP(next).
-// Leaves the residual rows of `next` in r.
-// (function attributes and the partial-sum buffer are set up by sart_tile_prepare, on the caller's thread and stream)
-static int sart_tile_prepare(tomo_engine *e, bool coop)
-{
-    if (!e->attr_st) {
-        const void *forms[] = {(const void *)k_sart_tile<true, false, true>, (const void *)k_sart_tile<true, false, false>,
-                               (const void *)k_sart_tile<false, false, true>, (const void *)k_sart_tile<false, false, false>,
-                               (const void *)k_sart_tile<true, true, true>, (const void *)k_sart_tile<true, true, false>,
-                               (const void *)k_sart_tile<true, false, true, true>, (const void *)k_sart_tile<true, false, false, true>};
-        for (const void *f : forms) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS_V * 16));
-        e->attr_st = true;
-    }
-    const size_t pbytes = (size_t)std::max<uint32_t>(1, e->st_max_ids) * e->sx * sizeof(float);
-    if (!e->st_partial) {
-        int rc = dev_alloc(e, GEOMETRY, (void **)&e->st_partial, pbytes, true);
-        if (rc) return rc;
-    }
-    if (coop && !e->st_partial2) {
-        int rc = dev_alloc(e, GEOMETRY, (void **)&e->st_partial2, pbytes, true);
-        if (rc) return rc;
-        if ((rc = dev_alloc(e, GEOMETRY, (void **)&e->st_flags, (size_t)e->n * (e->sxc / 64) * sizeof(uint32_t), true))) return rc;
-        // workgroups that start together: the reducer duty is dealt to that many (2 per CU by LDS; any value is correct)
-        int per_cu = 0;
-        hipDeviceProp_t prop;
-        HIPCHK(hipGetDeviceProperties(&prop, e->device));
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_sart_tile<true, true, true>, ST_THREADS, ST_LDS_V * 16));
-        e->st_resident = std::max(1, per_cu) * std::max(1, prop.multiProcessorCount);
-    }
-    return TOMO_OK;
-}
-
-// residual rows of angle `next` from the tile partial sums in `partial` (k_resid_finish)
-static int launch_resid_finish_tile(tomo_engine *e, const Sub &sb, const float *partial, int next, float *r, bool sum = false)
-{
-    const Chunks ch = chunks64(e, sb);
-    const int vec = sub_vec(e, sb), nchunk = ch.n / vec;
-    dim3 grid((unsigned)((int64_t)e->n * nchunk)), block(256);
-    // sum: plain row sums (chained ART: k_art_chain forms the residuals)
-    with_vec(vec, [&](auto V) { with_flag(sum, [&](auto S) {
-        hipLaunchKernelGGL((k_resid_finish<V(), S()>), grid, block, 0, sb.stream, partial, e->d_st_row_first, e->d_st_row_nseg, e->cur_b, e->d_rowsum, r, next * e->n, e->n,
-                           nchunk, e->sx, ch.c0 / vec);
-    }); });
-    LAUNCHCHK();
-    return TOMO_OK;
-}
-
-// finish = false leaves the partial sums of `next` in `partial` for the next link's reducer duty (cooperative chain)
-// ART: the fused step of the chained ART sweep (r = the rows k_art_chain left for `prev`; the finish stores plain row sums into
-// fp_out, from which k_art_chain forms the rows of `next`)
-template <bool FUSED, bool ART = false>
-static int launch_sart_tile(tomo_engine *e, const Sub &sb, float *x, int prev, int next, float *r, float beta,
-                            float *partial = nullptr, bool finish = true, int64_t key = -1, float *fp_out = nullptr)
-{
-    const Chunks ch = chunks64(e, sb);
-    const size_t nt = (size_t)e->st_ntiles;
-    if (!partial) partial = e->st_partial;
-    {
-        ProfScope ps(e, FUSED ? TOMO_K_SART_FUSED : TOMO_K_FP_ANGLE, sb.stream, key);
-        dim3 grid((unsigned)(8 * ((e->st_ntiles + 7) / 8) * ch.n)), block(ST_THREADS);
-        with_flag(slab_streams(e), [&](auto NT) {
-            hipLaunchKernelGGL((k_sart_tile<FUSED, false, NT(), ART && FUSED>), grid, block, ST_LDS_V * 16, sb.stream, x, x,
-                               FUSED ? e->d_st_cell + (size_t)prev * nt * ST_PIX : nullptr, FUSED ? e->d_st_win + (size_t)prev * nt : nullptr,
-                               FUSED ? r + (size_t)prev * e->n * e->sx : nullptr, beta,
-                               e->d_st_seg + (size_t)next * nt * ST_MAXSEG, e->d_st_segid + (size_t)next * nt * ST_MAXSEG, e->d_st_ent, partial,
-                               e->n, e->sx, e->st_tiles_z, e->st_ntiles, ch.n, ch.c0, e->sart_skip_same, StCoop{});
-        });
-        LAUNCHCHK();
-    }
-    if (ART) return launch_resid_finish_tile(e, sb, partial, next, fp_out, true);
-    return finish ? launch_resid_finish_tile(e, sb, partial, next, r) : TOMO_OK;
-}
-
-// cooperative link: residual rows of `prev` from p_read (reducer duty of the first workgroups), BP(prev) + FP(next) -> p_write
-static int launch_sart_coop(tomo_engine *e, const Sub &sb, float *x, int prev, int next, float *r, float beta,
-                            const float *p_read, float *p_write, uint32_t epoch, int64_t key = -1)
-{
-    const Chunks ch = chunks64(e, sb);
-    const size_t nt = (size_t)e->st_ntiles;
-    ProfScope ps(e, TOMO_K_SART_FUSED, sb.stream, key);
-    const unsigned nblocks = (unsigned)(8 * ((e->st_ntiles + 7) / 8) * ch.n);
-    StCoop co;
-    co.p_read = p_read;
-    co.row_first = e->d_st_row_first + (size_t)prev * e->n;
-    co.row_nseg = e->d_st_row_nseg + (size_t)prev * e->n;
-    co.b = e->cur_b + (size_t)prev * e->n * e->sx;
-    co.rowsum = e->d_rowsum + (size_t)prev * e->n;
-    co.r_out = r + (size_t)prev * e->n * e->sx;
-    co.flags = e->st_flags;
-    co.epoch = epoch;
-    co.nitems = e->n * ch.n;
-    co.nred = (int)std::min<unsigned>(nblocks, (unsigned)std::max(1, e->st_resident));
-    co.nchunk_all = e->sxc / 64;
-    co.spin = e->sart_coop_spin;
-    with_flag(slab_streams(e), [&](auto NT) {
-        hipLaunchKernelGGL((k_sart_tile<true, true, NT()>), dim3(nblocks), dim3(ST_THREADS), ST_LDS_V * 16, sb.stream, x, x,
-                           e->d_st_cell + (size_t)prev * nt * ST_PIX, e->d_st_win + (size_t)prev * nt, r + (size_t)prev * e->n * e->sx, beta,
-                           e->d_st_seg + (size_t)next * nt * ST_MAXSEG, e->d_st_segid + (size_t)next * nt * ST_MAXSEG, e->d_st_ent, p_write,
-                           e->n, e->sx, e->st_tiles_z, e->st_ntiles, ch.n, ch.c0, e->sart_skip_same, co);
-    });
     LAUNCHCHK();
     return TOMO_OK;
 }

@@ -21,10 +21,10 @@ int tomo_get_option(tomo_engine *e, const char *name, int *value)
     if (std::strcmp(name, "sart_resident_ready") == 0) { *value = e->rs_ok ? 1 : 0; return TOMO_OK; }
     if (std::strcmp(name, "sart_resident_active") == 0) { *value = (e->rs_ok && e->sart_resident != 0) ? 1 : 0; return TOMO_OK; }
     if (std::strcmp(name, "sart_resident_spin") == 0) { *value = (int)std::min<uint32_t>(e->rs_spin_limit, 0x7FFFFFFFu); return TOMO_OK; }
-    if (std::strcmp(name, "sart_resident_fallbacks") == 0) { *value = e->rs_fallbacks; return TOMO_OK; }            // sweeps that needed the streamed chain
-    if (std::strcmp(name, "sart_resident_fallback_chunks") == 0) { *value = e->rs_fallback_chunks; return TOMO_OK; } // ... and the 64-slice chunks it swept
-    if (std::strcmp(name, "sart_resident_skip") == 0) { *value = e->rs_skip; return TOMO_OK; }                       // sweeps the resident form still sits out
-    if (std::strcmp(name, "sart_resident_last_code") == 0) { *value = e->rs_last_code; return TOMO_OK; }             // 1 residual rows, 2 tile sums (0: the commit)
+    if (std::strcmp(name, "sart_resident_fallbacks") == 0) { *value = e->rs.fallbacks; return TOMO_OK; }            // sweeps that needed the streamed chain
+    if (std::strcmp(name, "sart_resident_fallback_chunks") == 0) { *value = e->rs.fallback_chunks; return TOMO_OK; } // ... and the 64-slice chunks it swept
+    if (std::strcmp(name, "sart_resident_skip") == 0) { *value = e->rs.skip; return TOMO_OK; }                       // sweeps the resident form still sits out
+    if (std::strcmp(name, "sart_resident_last_code") == 0) { *value = e->rs.last_code; return TOMO_OK; }             // 1 residual rows, 2 tile sums (0: the commit)
     if (std::strcmp(name, "table_kib") == 0) { *value = (int)std::min<size_t>(e->table_bytes >> 10, 0x7FFFFFFF); return TOMO_OK; }   // device tables built at creation
     if (std::strcmp(name, "create_ms") == 0) { *value = (int)std::min(e->create_ms + 0.5, 2147483647.0); return TOMO_OK; }           // what creating this engine took
     if (std::strcmp(name, "tv_halo_fold") == 0) { *value = e->tv_halo_fold; return TOMO_OK; }
@@ -45,7 +45,7 @@ int tomo_set_option(tomo_engine *e, const char *name, int value)
     if (std::strcmp(name, "fp_all_lpr") == 0) { e->fp_all_lpr = (value == 16 || value == 32) ? value : 0; return TOMO_OK; }
     if (std::strcmp(name, "art_chain") == 0) { e->art_chain = value ? 1 : 0; return TOMO_OK; }
     if (std::strcmp(name, "sart_tile") == 0) { e->sart_tile = value ? 1 : 0; return TOMO_OK; }
-    if (std::strcmp(name, "sart_resident") == 0) { e->sart_resident = value < 0 ? -1 : (value ? 1 : 0); e->rs_skip = e->rs_backoff = 0; return TOMO_OK; }
+    if (std::strcmp(name, "sart_resident") == 0) { e->sart_resident = value < 0 ? -1 : (value ? 1 : 0); e->rs.skip = e->rs.backoff = 0; return TOMO_OK; }
     if (std::strcmp(name, "sart_resident_spin") == 0) { e->rs_spin_limit = value < 0 ? (1u << 21) : (uint32_t)value; return TOMO_OK; }   // polls before a wait gives up (< 0: the default; tests: tiny, 0 = at the first look)
     if (std::strcmp(name, "sart_resident_test_fail") == 0) { e->rs_test_fail = std::max(0, value); return TOMO_OK; }   // tests: chunk + 1 that refuses to commit
     if (std::strcmp(name, "fp_reuse") == 0) { e->fp_reuse = value != 0; g_clear(e); e->yk_claim.valid = false; return TOMO_OK; }
@@ -127,12 +127,12 @@ int tomo_profile_read2(tomo_engine *e, int kernel, int64_t *launches, double *to
     }
     if (busy_ms) {
         std::sort(iv.begin(), iv.end());
-        double busy = 0; float cur_a = 0, cur_b = -1;
+        double busy = 0; float run_a = 0, run_b = -1;
         for (auto &q : iv) {
-            if (cur_b < cur_a || q.first > cur_b) { if (cur_b >= cur_a) busy += cur_b - cur_a; cur_a = q.first; cur_b = q.second; }
-            else cur_b = std::max(cur_b, q.second);
+            if (run_b < run_a || q.first > run_b) { if (run_b >= run_a) busy += run_b - run_a; run_a = q.first; run_b = q.second; }
+            else run_b = std::max(run_b, q.second);
         }
-        if (cur_b >= cur_a) busy += cur_b - cur_a;
+        if (run_b >= run_a) busy += run_b - run_a;
         *busy_ms = busy;
     }
     *launches = (int64_t)(p.used / 2);

@@ -10,6 +10,7 @@
 #include "sysmat.h"
 #include "resident.h"
 #include "dev_pool.h"
+#include "sart_host.h"
 
 #include <dlfcn.h>
 #if __has_include(<rccl/rccl.h>)
@@ -198,17 +199,7 @@ struct tomo_engine {
     uint32_t *d_fl_ptr = nullptr, *d_fl_fptr = nullptr;
     float *d_fl_zero = nullptr;
     bool attr_fp = false, attr_bp = false, attr_st = false;   // dynamic-LDS limits raised on this engine's device
-    // The SART chain of one slab is a string of dependent launches (tile step -> residual finish -> tile step ...): ~5.7 us of
-    // idle chip after each and a tail of partly filled CUs at the end of each.  Slices are independent, so the sweep CAN run as
-    // two sub-slabs on two streams, each filling the other's gaps ("sart_streams" = 2).  Measured (round 2, per sweep): two
-    // separate 256-slice engines side by side 18.0 ms against 20.7 for one 512-slice engine -- but two sub-slabs of ONE slab
-    // interleave inside every pixel row (1 KB of every 2 KB) and reached only 19.4 ms at 512 slices and 51.3 against 40.6 ms
-    // at 1024: two kernels striding over alternate halves of the same rows collide in the memory system.  With the streamed tile
-    // accesses and the skipped stores of round 2 the gain at 512 slices grew to 5.5 % of the ASD-POCS step (23.4 -> 22.1 ms),
-    // so the default is now 0 = automatic (the rule is in sart_impl); the sub-slabs split at 64-slice chunks and run their
-    // per-row kernels at the widest vector that fits (k_bp_angle writes its roundings out, so every width gives the same bits).
-    // sub_c0 / sub_nc: the 64-slice chunk range the launch helpers address (0 / 0 = whole slab).
-    int sart_streams = 0, sub_c0 = 0, sub_nc = 0;
+    int sart_streams = 0;                        // chains a SART / ART sweep runs as: 0 = automatic, 1 = one, 2..4 = that many (chain_count, run_chains)
     static constexpr int MAX_CHAINS = 4;
     hipStream_t sub_stream[MAX_CHAINS] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_sfork = nullptr, ev_sjoin[MAX_CHAINS] = {nullptr, nullptr, nullptr, nullptr};
@@ -242,22 +233,19 @@ struct tomo_engine {
     uint16_t *d_rs_rl = nullptr;
     rs_u64 *rs_pb = nullptr, *rs_rb = nullptr;     // granules {value, tag}: tile sums, residual rows
     size_t rs_pb_bytes = 0, rs_rb_bytes = 0;
-    int *d_rs_angs = nullptr;                      // angle of every step of the sweep in flight
-    size_t rs_angs_cap = 0;
+    int *d_rs_angs = nullptr; size_t rs_angs_cap = 0;   // angle of every step of the sweep in flight, and the steps it has room for
     std::vector<int> rs_angs_host;                 // (what d_rs_angs holds: an unchanged sequence is not uploaded again)
     int *rs_abort = nullptr, *d_rs_abort = nullptr; // pinned host word / device word a workgroup sets when a bounded spin gave up
     // fail-safe (round 6): a chunk is stored by all of its workgroups or by none (rs_commit); d_rs_commit = the chunks' commit words,
     // rs_done = pinned [chunk]: the sequence number of the launch that stored it.  Chunks that did not commit are swept by the streamed
-    // chain, and the resident form then sits out rs_skip sweeps (doubling up to 64 while the failures go on; "sart_resident" = 1 insists)
+    // chain, and the resident form then sits out rs.skip sweeps (doubling up to 64 while the failures go on; "sart_resident" = 1 insists)
     unsigned *d_rs_commit = nullptr;
     int *rs_done = nullptr;
-    uint32_t rs_seq = 0, rs_commit_base = 0;
-    bool rs_commit_dirty = false;
+    RsLedger rs;                                   // the launches' counters: tags, commit base, sequence number, sit-out (sart_host.h)
+    int rs_test_fail = 0;                          // tests: chunk + 1 that refuses to commit
+    uint32_t rs_spin_limit = 1u << 21;             // polls before a wait of the resident kernel gives up
     size_t table_bytes = 0;                        // device bytes of the tables built at creation (everything but volumes, sinograms, halos)
     double create_ms = 0.0;                        // wall clock of the creation (matrix, tables, uploads)
-    int rs_fallbacks = 0, rs_fallback_chunks = 0, rs_skip = 0, rs_backoff = 0, rs_last_code = 0, rs_test_fail = 0;
-    uint32_t rs_epoch = 0;                         // tags handed out so far (a granule's tag is unique per sweep, chunk round and step)
-    uint32_t rs_spin_limit = 1u << 21;
     int art_tile = 1;                              // chained ART sweep as fused tile steps (k_sart_tile ART) instead of k_fp_rows + k_bp_art per angle
     int sart_skip_same = 1;                        // k_sart_tile stores only the 256-byte pieces whose bits changed (in place)
     int sart_nt = -1;                              // tile accesses: -1 streaming form by slab size (slab_streams), 0 plain, 1 streaming
@@ -278,11 +266,10 @@ struct tomo_engine {
     float *sino[TOMO_SINO_SLOTS] = {};
     int fgp_target = TOMO_VOL_RECON;
     int tv_target = TOMO_VOL_RECON;               // volume the tv_gd / tv_grad / tv_update forms act on (tomo_tv_set_target)
-    float *cur_b = nullptr;
     float *cg_p = nullptr, *cg_z = nullptr, *cg_w = nullptr, *fbp_h = nullptr;   // CGLS direction / A^T r / A p; WBP kernel
     double *cg_sums = nullptr;                    // 2*sx per-slice sums
     double *cg_part = nullptr;                    // 1024 x sx: the workgroups' partial sums of a per-slice reduction
-    float *cg_coef = nullptr;                     // sx per-slice coefficients                      // data sinogram of the SART call in progress
+    float *cg_coef = nullptr;                     // sx per-slice coefficients
     float *tvg = nullptr;                         // TV gradient tensor; doubles as FGP "D"
     float *fgp_p[3] = {nullptr, nullptr, nullptr};
     float *fgp_q[3] = {nullptr, nullptr, nullptr};   // ping-pong partners for the fused FGP iteration
@@ -448,7 +435,7 @@ struct Sub {
     int vec = 0;       // vector width of the per-row kernels on this sub-slab (0: the engine's); divides c0 and nc
 };
 static int sub_vec(const tomo_engine *e, const Sub &sb) { return sb.nc && sb.vec ? sb.vec : e->vec; }
-static Sub whole(const tomo_engine *e) { return Sub{e->stream, e->sub_c0, e->sub_nc}; }
+static Sub whole(const tomo_engine *e) { return Sub{e->stream}; }
 
 // Where a projection or a reduction of the whole slab runs: the stream, the partial sums its scalar is gathered in, and the index that
 // picks the lane's FP scratch (FpFamily::part) and its open flag (part_open).  Passed explicitly: the main sequence and the evaluation
@@ -513,6 +500,7 @@ static int grid_1d(int64_t n4) { int64_t b = (n4 + 255) / 256; return (int)std::
 
 #include "engine_launch.inc"
 #include "engine_create.inc"
+#include "engine_sart.inc"
 
 extern "C" {
 
