@@ -88,6 +88,29 @@ int tomo_set_volume(tomo_engine *e, int vol, const float *data);        /* all s
 int tomo_get_volume(tomo_engine *e, int vol, float *data);
 int tomo_set_slice(tomo_engine *e, int vol, int s, const float *img);   /* :104-106 setOriginalVolume / setRecon */
 int tomo_get_slice(tomo_engine *e, int vol, int s, float *img);         /* :452 getRecon */
+/* ---- the same data calls on DEVICE buffers of the caller --------------------------------------------------------------------
+ * For a host that already has the tilt series on the GPU, or wants the reconstruction there (the reference only ever hands over
+ * host arrays: gpu/reconstructor.py:54-56 packs and uploads, :207-215 downloads and converts).  `dev` is plain device memory of
+ * the engine's device holding `nelems` elements of `dtype`, dense: a volume as [Nslice][Ny][Nz], a sinogram in `layout`.  The
+ * conversion kernel reads or writes the caller's buffer directly: no staging buffer is allocated or touched, and the call does
+ * not wait on the host.  `hip_stream` (hipStream_t, NULL = the default stream) is the stream on which the caller produced the
+ * data (set) or will consume it (get): the engine's stream is ordered behind it before the kernel and it is ordered behind the
+ * engine's stream after the kernel, with events on the device, so the caller may also overwrite or free a buffer it has set from
+ * that stream.  The same stream as the engine's (tomo_set_stream) needs no event.
+ * Checked before anything is enqueued, TOMO_ERR_ARG otherwise: dtype and layout are one of the constants; nelems is Nslice*Ny*Nz
+ * (volume) or Nslice*Nproj*Nray (sinogram); hipPointerGetAttributes knows `dev` as device memory (not pinned, managed or pageable
+ * host memory, not NULL) of the engine's device, and its allocation holds nelems elements from `dev` on.
+ * A set writes the padding slices of the engine's layout as zero; a get writes nothing outside the nelems elements.  Slot
+ * bookkeeping (write versions, the model sinogram's claim, the FISTA state) is that of the host calls. */
+enum tomo_dtype { TOMO_F32 = 0,             /* float32 */
+                  TOMO_F64 = 1 };           /* float64: rounded to nearest even on the way in (a C cast), exact on the way out */
+enum tomo_sino_layout { TOMO_SINO_PACKED = 0,   /* [Nslice][Nproj][Nray]: the host calls' layout, index angle*Nray+ray */
+                        TOMO_SINO_PUBLIC = 1 }; /* [Nslice][Nray][Nproj]: what TomoGPU is given (gpu/reconstructor.py:54-56 transposes it) */
+int tomo_set_volume_device(tomo_engine *e, int vol, const void *dev, int dtype, int64_t nelems, void *hip_stream);
+int tomo_get_volume_device(tomo_engine *e, int vol, void *dev, int dtype, int64_t nelems, void *hip_stream);
+int tomo_set_sinogram_device(tomo_engine *e, int which, const void *dev, int dtype, int layout, int64_t nelems, void *hip_stream);
+/* which = TOMO_SINO_YK_MODEL reads as in tomo_get_sinogram */
+int tomo_get_sinogram_device(tomo_engine *e, int which, void *dev, int dtype, int layout, int64_t nelems, void *hip_stream);
 int tomo_restart_recon(tomo_engine *e);                                 /* :462-468 restart_recon */
 int tomo_copy_volume(tomo_engine *e, int dst, int src);                 /* :404 copy_recon = (TEMP <- RECON) */
 /* volume of another engine with the same slab shape (rebuilding the tilt geometry keeps the reconstruction:
@@ -397,6 +420,8 @@ int tomo_set_option(tomo_engine *e, const char *name, int value);
  * "sart_resident_skip" (sweeps the resident form still sits out), "sart_resident_last_code" (what the last give-up waited for:
  * 1 residual rows, 2 tile sums, 0 the commit),
  * "table_kib" (device memory of the tables built at creation: every kernel family's, eagerly), "create_ms" (what creation took),
+ * "stage_bytes" (bytes of the staging buffer the HOST data calls copy through, clamped to 2^31 - 1; 0 = never allocated: the device
+ * data calls, tomo_set_volume_device ..., neither allocate nor use it),
  * "form_fp" / "form_bp" / "form_sart": which kernel family the all-angle forward projection, the all-angle back projection and the
  * SART sweep of THIS engine run as under the options in force (tomo_form; one function of the engine decides it for the launchers
  * and for this query: tomo_engine.hip select_forms) */

@@ -16,6 +16,8 @@ SINO_YK_MODEL = 1000     # read-only: A * yk as tomo_fista_project_yk formed it
 VOL_USER0 = 5
 S_DD, S_DIFF, S_TV, S_GNORM, S_RMSE, S_COST, S_L1, S_DIFF2, S_GNORM_ALL, S_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 16
 FIELD_FGP_D, FIELD_FGP_P1 = 100, 101
+F32, F64 = 0, 1                       # tomo_dtype of the device data calls
+SINO_PACKED, SINO_PUBLIC = 0, 1       # tomo_sino_layout: [s][angle][ray] (the host calls') / [s][ray][angle] (what TomoGPU is given)
 K_BP_ANGLE, K_FP_ANGLE, K_TV_GRAD, K_TV_UPDATE, K_FGP_OBJ, K_FGP_GRAD, K_SART_FUSED, K_FP_TILE, K_BP_TILE, K_FP_REDUCE, K_SART_RESIDENT, K_PDHG_TV = range(12)
 # tomo_form (tomo_get_option "form_fp" / "form_bp" / "form_sart"): the kernel family an operation of an engine runs as
 FORM_FP = ("rows", "tile", "strip", "list")
@@ -42,6 +44,10 @@ SIGNATURES = {
     "tomo_get_volume": [_p, _i, _p],
     "tomo_set_slice": [_p, _i, _i, _p],
     "tomo_get_slice": [_p, _i, _i, _p],
+    "tomo_set_volume_device": [_p, _i, _p, _i, _i64, _p],
+    "tomo_get_volume_device": [_p, _i, _p, _i, _i64, _p],
+    "tomo_set_sinogram_device": [_p, _i, _p, _i, _i, _i64, _p],
+    "tomo_get_sinogram_device": [_p, _i, _p, _i, _i, _i64, _p],
     "tomo_restart_recon": [_p],
     "tomo_copy_volume": [_p, _i, _i],
     "tomo_copy_volume_from": [_p, _i, _p, _i],

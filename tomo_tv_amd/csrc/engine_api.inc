@@ -79,6 +79,7 @@ int tomo_destroy(tomo_engine *e)
     comm_release(e);
     if (e->ev_sfork) (void)hipEventDestroy(e->ev_sfork);
     if (e->ev_peer) (void)hipEventDestroy(e->ev_peer);
+    if (e->ev_io) (void)hipEventDestroy(e->ev_io);
     if (e->ev_snap) (void)hipEventDestroy(e->ev_snap);
     if (e->h_snap) (void)hipHostFree(e->h_snap);
     if (e->rs_abort) (void)hipHostFree(e->rs_abort);
@@ -242,6 +243,46 @@ int tomo_get_slice(tomo_engine *e, int vol, int s, float *img)
     HIPCHK(hipMemcpyAsync(img, e->stage, e->npix * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return TOMO_OK;
+}
+
+// ---- data in / out of device buffers of the caller (no staging buffer, no host wait) ------------------------------------------
+// (check_device_buffer, io_fence, io_args, io_launch: engine_launch.inc)
+int tomo_set_volume_device(tomo_engine *e, int vol, const void *dev, int dtype, int64_t nelems, void *hip_stream)
+{
+    NEED(e);
+    int rc = io_args(e, dev, dtype, TOMO_SINO_PACKED, nelems, e->npix); if (rc) return rc;
+    if ((rc = order_after_async(e))) return rc;
+    float *dst; if ((rc = get_vol(e, vol, &dst))) return rc;
+    return io_launch<true>(e, const_cast<void *>(dev), dst, e->npix, dtype, TOMO_SINO_PACKED, (hipStream_t)hip_stream);
+}
+
+int tomo_get_volume_device(tomo_engine *e, int vol, void *dev, int dtype, int64_t nelems, void *hip_stream)
+{
+    NEED(e);
+    int rc = io_args(e, dev, dtype, TOMO_SINO_PACKED, nelems, e->npix); if (rc) return rc;
+    float *src; if ((rc = get_vol_ro(e, vol, &src))) return rc;
+    return io_launch<false>(e, dev, src, e->npix, dtype, TOMO_SINO_PACKED, (hipStream_t)hip_stream);
+}
+
+int tomo_set_sinogram_device(tomo_engine *e, int which, const void *dev, int dtype, int layout, int64_t nelems, void *hip_stream)
+{
+    NEED(e);
+    int rc = io_args(e, dev, dtype, layout, nelems, e->nrows); if (rc) return rc;
+    if ((rc = order_after_async(e))) return rc;      // (an evaluation on the second stream may still read B or G)
+    float *dst; if ((rc = sino_slot(e, which, &dst))) return rc;
+    return io_launch<true>(e, const_cast<void *>(dev), dst, e->nrows, dtype, layout, (hipStream_t)hip_stream);
+}
+
+int tomo_get_sinogram_device(tomo_engine *e, int which, void *dev, int dtype, int layout, int64_t nelems, void *hip_stream)
+{
+    NEED(e);
+    int rc = io_args(e, dev, dtype, layout, nelems, e->nrows); if (rc) return rc;
+    float *src;
+    if (which == TOMO_SINO_YK_MODEL) {                   // the extrapolated point's projection, while it is one
+        src = const_cast<float *>(projection_in_hand(e, TOMO_VOL_YK));
+        if (!src) return fail(TOMO_ERR_STATE, "no projection of the extrapolated point in hand (tomo_fista_project_yk)");
+    } else if ((rc = sino_slot(e, which, &src))) return rc;
+    return io_launch<false>(e, dev, src, e->nrows, dtype, layout, (hipStream_t)hip_stream);
 }
 
 int tomo_restart_recon(tomo_engine *e)

@@ -1,7 +1,8 @@
 // engine_launch.inc -- part of tomo_engine.hip (ONE translation unit: the kernels are templates and asm blocks in headers; the host side is
 // split by topic into files that tomo_engine.hip includes in order).  This part: which kernel family runs (select_forms, select_sart) and the
 // launch helpers of the projectors (the steps of a SART sweep are in engine_sart.inc).  The forward projectors take the Lane they run on; the three
-// partial-sum families of the all-angle one (tile, strip, list) differ in their main kernel only and share one pass loop (fp_passes).
+// partial-sum families of the all-angle one (tile, strip, list) differ in their main kernel only and share one pass loop (fp_passes).  Last: the
+// checks, the stream ordering and the launch of the data calls on device buffers of the caller (tomo_set_*_device / tomo_get_*_device).
 
 // ---- run-time value -> template argument ----------------------------------------------------------------------
 // The ONE way a run-time value picks a kernel instantiation: f is called with a std::integral_constant of the value (the last
@@ -302,4 +303,61 @@ static int launch_bp_all(tomo_engine *e, float *x, const float *r, const float *
     });
     LAUNCHCHK();
     return TOMO_OK;
+}
+
+// ---- data in / out of device buffers of the caller (tomo_set_*_device / tomo_get_*_device, engine_api.inc) -----------------------
+// ext must be plain device memory of the engine's device, `bytes` long from ext on: asked of the runtime before anything is enqueued
+static int check_device_buffer(tomo_engine *e, const void *ext, size_t bytes)
+{
+    if (!ext) return fail(TOMO_ERR_ARG, "null device pointer");
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, ext) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(TOMO_ERR_ARG, "the pointer is not known to the HIP runtime (pageable host memory?)");
+    }
+    if (at.type != hipMemoryTypeDevice) return fail(TOMO_ERR_ARG, "the pointer is not plain device memory (pinned, managed or unregistered host memory)");
+    if (at.device != e->device) return fail(TOMO_ERR_ARG, "the buffer lives on device " + std::to_string(at.device) + ", the engine on device " + std::to_string(e->device));
+    hipDeviceptr_t base = nullptr; size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(ext)) != hipSuccess) { (void)hipGetLastError(); return TOMO_OK; }   // (no range known: the type check stands alone)
+    if ((const char *)ext + bytes > (const char *)base + size) return fail(TOMO_ERR_ARG, "the buffer's allocation ends before nelems elements");
+    return TOMO_OK;
+}
+
+// Both streams are ordered both ways around the kernel, by events on the device: the engine's stream starts behind what the caller's
+// stream did to the buffer (produced it; filled or freed what a get overwrites), the caller's stream continues behind the kernel (consumes a
+// get; may overwrite or free what a set read).  The same stream on both sides needs neither.
+static int io_fence(tomo_engine *e, hipStream_t from, hipStream_t to)
+{
+    if (from == to) return TOMO_OK;
+    if (!e->ev_io) HIPCHK(hipEventCreateWithFlags(&e->ev_io, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(e->ev_io, from));
+    HIPCHK(hipStreamWaitEvent(to, e->ev_io, 0));
+    return TOMO_OK;
+}
+
+static int io_args(tomo_engine *e, const void *ext, int dtype, int layout, int64_t nelems, int64_t m)
+{
+    if (dtype != TOMO_F32 && dtype != TOMO_F64) return fail(TOMO_ERR_ARG, "bad dtype (TOMO_F32 or TOMO_F64)");
+    if (layout != TOMO_SINO_PACKED && layout != TOMO_SINO_PUBLIC) return fail(TOMO_ERR_ARG, "bad layout (TOMO_SINO_PACKED or TOMO_SINO_PUBLIC)");
+    if (nelems != (int64_t)e->nx * m) return fail(TOMO_ERR_ARG, "nelems is " + std::to_string(nelems) + ", the slab has " + std::to_string((int64_t)e->nx * m) + " elements");
+    if (m > 0x7FFFFFFF) return fail(TOMO_ERR_ARG, "more than 2^31 rows");
+    return check_device_buffer(e, ext, (size_t)nelems * (dtype == TOMO_F64 ? sizeof(double) : sizeof(float)));
+}
+
+// the conversion kernel between ext ([nx][m], dtype, layout) and dev ([m][sx]) on the engine's stream, fenced against `caller`
+template <bool IN>
+static int io_launch(tomo_engine *e, void *ext, float *dev, int64_t m, int dtype, int layout, hipStream_t caller)
+{
+    int rc = io_fence(e, caller, e->stream);
+    if (rc) return rc;
+    const dim3 grid((unsigned)((m + IO_TJ - 1) / IO_TJ), (unsigned)(e->sx / IO_TS)), block(256);
+    const size_t esz = dtype == TOMO_F64 ? sizeof(double) : sizeof(float);
+    const bool vec = m % 4 == 0 && (uintptr_t)ext % (4 * esz) == 0;
+    with_flag(dtype == TOMO_F64, [&](auto f64) { with_flag(layout == TOMO_SINO_PUBLIC, [&](auto pub) { with_flag(vec, [&](auto v) {
+        using T = std::conditional_t<decltype(f64)::value, double, float>;
+        if constexpr (IN) hipLaunchKernelGGL((k_io_in<T, decltype(pub)::value, decltype(v)::value>), grid, block, 0, e->stream, (const T *)ext, dev, e->nx, m, e->sx, e->np, e->n);
+        else hipLaunchKernelGGL((k_io_out<T, decltype(pub)::value, decltype(v)::value>), grid, block, 0, e->stream, dev, (T *)ext, e->nx, m, e->sx, e->np, e->n);
+    }); }); });
+    LAUNCHCHK();
+    return io_fence(e, e->stream, caller);
 }

@@ -1,4 +1,4 @@
-// kernels_common.hip.h -- vector helpers, block reductions, layout conversion at the host boundary
+// kernels_common.hip.h -- vector helpers, block reductions, layout conversion at the host boundary and at the device boundary
 // Part of kernels.hip.h (include that, not this: the families share helpers and constants in the order kernels.hip.h lists them).
 #pragma once
 
@@ -124,6 +124,97 @@ __global__ __launch_bounds__(256) void k_transpose_out(const float *__restrict__
         int s = s0 + r;
         int64_t mm = m0 + tx;
         if (s < ns && mm < m) dst[(int64_t)s * m + mm] = tile[tx][r];
+    }
+}
+
+// ---- layout conversion at the device boundary (tomo_set_*_device / tomo_get_*_device) ------------------------------------
+// The caller's buffer ext is dense [ns][m] of T (float or double), the engine's dev is [m][sx] floats.  With PUBLIC the caller's
+// sinogram is [s][ray][angle]: column j = ray * nang + angle of ext is row angle * nray + ray of dev, so the pack of
+// pytvlib.pack_tilt_series is a permutation of the ROWS dev is addressed by -- ext is still read along its contiguous index and
+// dev still written along slices.  A workgroup moves 32 columns x 64 slices as two 32 x 32 tiles through LDS; every thread moves
+// four consecutive columns on the ext side and four consecutive slices on the dev side (16 bytes of float each; VEC: as one access,
+// which needs m % 4 == 0 and a 16-byte aligned ext).  Tile pitch 33: in a 32-lane group of a ds_read_b32 / ds_write_b32 eight
+// lanes x 4 columns of four consecutive rows fall on banks 4 l + r + const (mod 32), all distinct, on either side.
+constexpr int IO_TJ = 32, IO_TS = 64;
+
+template <typename T> struct IoVec4;
+template <> struct IoVec4<float> { typedef float T __attribute__((ext_vector_type(4))); };
+template <> struct IoVec4<double> { typedef double T __attribute__((ext_vector_type(4))); };
+
+template <bool PUBLIC>
+__device__ __forceinline__ int64_t io_row(int64_t j, int nang, int nray)
+{
+    if constexpr (PUBLIC) { uint32_t ray = (uint32_t)j / (uint32_t)nang, ang = (uint32_t)j - ray * (uint32_t)nang; return (int64_t)ang * nray + ray; }
+    else return j;
+}
+
+// ext -> dev; T = double rounds to nearest even (the conversion of a C cast); slices ns <= s < sx are written as zero
+template <typename T, bool PUBLIC, bool VEC>
+__global__ __launch_bounds__(256) void k_io_in(const T *__restrict__ ext, float *__restrict__ dev, int ns, int64_t m, int sx,
+                                               int nang, int nray)
+{
+    __shared__ float tile[2][32][33];
+    const int64_t j0 = (int64_t)blockIdx.x * IO_TJ;
+    const int s0 = blockIdx.y * IO_TS;
+    const int r = threadIdx.x >> 3, c = (threadIdx.x & 7) * 4;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int s = s0 + 32 * h + r;
+        const int64_t j = j0 + c;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (s < ns) {
+            const T *p = ext + (int64_t)s * m + j;
+            if constexpr (VEC) {
+                if (j < m) { typename IoVec4<T>::T q = *reinterpret_cast<const typename IoVec4<T>::T *>(p); for (int k = 0; k < 4; ++k) v[k] = (float)q[k]; }
+            } else {
+                for (int k = 0; k < 4; ++k) if (j + k < m) v[k] = (float)p[k];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) tile[h][r][c + k] = v[k];
+    }
+    __syncthreads();
+    const int64_t j = j0 + r;
+    if (j >= m) return;
+    float *q = dev + io_row<PUBLIC>(j, nang, nray) * sx + s0 + c;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        VecOf<4>::T v = {tile[h][c][r], tile[h][c + 1][r], tile[h][c + 2][r], tile[h][c + 3][r]};
+        *reinterpret_cast<VecOf<4>::T *>(q + 32 * h) = v;
+    }
+}
+
+// dev -> ext; writes ext[s][j] for s < ns, j < m only
+template <typename T, bool PUBLIC, bool VEC>
+__global__ __launch_bounds__(256) void k_io_out(const float *__restrict__ dev, T *__restrict__ ext, int ns, int64_t m, int sx,
+                                                int nang, int nray)
+{
+    __shared__ float tile[2][32][33];
+    const int64_t j0 = (int64_t)blockIdx.x * IO_TJ;
+    const int s0 = blockIdx.y * IO_TS;
+    const int r = threadIdx.x >> 3, c = (threadIdx.x & 7) * 4;
+    if (j0 + r < m) {
+        const float *q = dev + io_row<PUBLIC>(j0 + r, nang, nray) * sx + s0 + c;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            VecOf<4>::T v = *reinterpret_cast<const VecOf<4>::T *>(q + 32 * h);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) tile[h][c + k][r] = v[k];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int s = s0 + 32 * h + r;
+        const int64_t j = j0 + c;
+        if (s >= ns || j >= m) continue;
+        T *p = ext + (int64_t)s * m + j;
+        if constexpr (VEC) {
+            typename IoVec4<T>::T o = {(T)tile[h][r][c], (T)tile[h][r][c + 1], (T)tile[h][r][c + 2], (T)tile[h][r][c + 3]};
+            *reinterpret_cast<typename IoVec4<T>::T *>(p) = o;
+        } else {
+            for (int k = 0; k < 4; ++k) if (j + k < m) p[k] = (T)tile[h][r][c + k];
+        }
     }
 }
 

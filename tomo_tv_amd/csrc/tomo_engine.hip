@@ -163,6 +163,7 @@ struct tomo_engine {
     int gnorm_slot = TOMO_S_GNORM;                // scalar slot the TV update takes ||g||^2 from (slab groups: TOMO_S_GNORM_ALL)
     double *gnorm_override = nullptr;             // tomo_comm_tv_gd: the all-reduced sum g^2 (the slot itself keeps the slab's partial sum)
     hipEvent_t ev_peer = nullptr;                 // tomo_wait_for: "everything enqueued on this engine so far"
+    hipEvent_t ev_io = nullptr;                   // tomo_set_*_device / tomo_get_*_device: orders the caller's stream and the engine's
     float tv_last_eps = 1e-6f;
     float *tv_alt = nullptr, *halo_lo_alt = nullptr, *halo_hi_alt = nullptr;
     // fp_all_lpr: all-angle FP: lanes per ray of the narrow-chunk form (0 = wide form)

@@ -15,8 +15,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (FIELD_FGP_D, FIELD_FGP_P1, S_COST, S_COUNT, S_DD, S_DIFF, S_DIFF2, S_GNORM, S_GNORM_ALL, S_L1, S_RMSE, S_TV, SINO_B,
-                   SINO_G, VOL_ORIGINAL, VOL_RECON, VOL_RECON_OLD, VOL_TEMP, VOL_YK, check)
+from ._lib import (F32, F64, FIELD_FGP_D, FIELD_FGP_P1, S_COST, S_COUNT, S_DD, S_DIFF, S_DIFF2, S_GNORM, S_GNORM_ALL, S_L1, S_RMSE, S_TV, SINO_B,
+                   SINO_G, SINO_PACKED, SINO_PUBLIC, VOL_ORIGINAL, VOL_RECON, VOL_RECON_OLD, VOL_TEMP, VOL_YK, check)
 from .distributed import SlabComm, slab_partition
 
 
@@ -26,6 +26,29 @@ def _f32c(a):
 
 def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _torch_dtypes():
+    """torch dtype -> tomo_dtype of the device data calls (torch is imported only where tensors are used)"""
+    import torch
+    return {torch.float32: F32, torch.float64: F64}
+
+
+def is_tensor(a):
+    """True for a torch tensor (without importing torch for callers that never made one)."""
+    import sys
+    torch = sys.modules.get("torch")
+    return torch is not None and isinstance(a, torch.Tensor)
+
+
+def _on_device(t, device):
+    """Refuse, before any C call, what the device data calls cannot take: not a tensor, a CPU tensor, another device's tensor."""
+    if not is_tensor(t):
+        raise TypeError(f"a torch tensor is needed, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise ValueError("the tensor lives on the CPU: the tensor calls take device tensors (numpy arrays go through the host calls)")
+    if t.device.index != device:
+        raise ValueError(f"the tensor lives on cuda:{t.device.index}, the engine on cuda:{device}")
 
 
 class _SlabBackend:
@@ -205,6 +228,59 @@ class _SlabBackend:
         check(self.L.tomo_lipschitz(self.h, ctypes.byref(L)))
         return float(L.value)
 
+    # ---- bulk data as torch tensors on the engine's device (include/tomo_hip.h: tomo_set_*_device / tomo_get_*_device) ----
+    # The conversion kernels read / write the tensor's memory directly, ordered against torch's current stream by events.
+    def _stream(self):
+        import torch
+        return ctypes.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
+
+    def _sino_shape(self, layout):
+        if layout == SINO_PUBLIC:
+            return (self.nslice, self.nray, self.nproj)
+        if layout == SINO_PACKED:
+            return (self.nslice, self.nproj * self.nray)
+        raise ValueError(f"layout must be SINO_PACKED ({SINO_PACKED}) or SINO_PUBLIC ({SINO_PUBLIC})")
+
+    def _as_input(self, t, shape):
+        """``t`` as a dense float32 / float64 tensor of ``shape`` on this engine's device (converted there where it is neither)."""
+        import torch
+        _on_device(t, self.device)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"tensor must have shape {tuple(shape)}, got {tuple(t.shape)}")
+        if t.dtype not in _torch_dtypes():
+            t = t.to(torch.float32)
+        return t.contiguous()
+
+    def _as_output(self, shape, dtype, out):
+        import torch
+        dtype = dtype or torch.float32
+        if out is None:
+            if dtype not in _torch_dtypes():
+                raise TypeError("dtype must be torch.float32 or torch.float64")
+            return torch.empty(shape, dtype=dtype, device=torch.device("cuda", self.device))
+        _on_device(out, self.device)
+        if tuple(out.shape) != tuple(shape) or out.dtype not in _torch_dtypes() or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 / float64 tensor of shape {tuple(shape)}")
+        return out
+
+    def set_tilt_series_tensor(self, t, layout=SINO_PACKED, which=SINO_B):
+        t = self._as_input(t, self._sino_shape(layout))
+        self.c("set_sinogram_device", int(which), ctypes.c_void_p(t.data_ptr()), _torch_dtypes()[t.dtype], int(layout), t.numel(), self._stream())
+
+    def set_volume_tensor(self, t, which=VOL_RECON):
+        t = self._as_input(t, (self.nslice, self.nray, self.nray))
+        self.c("set_volume_device", int(which), ctypes.c_void_p(t.data_ptr()), _torch_dtypes()[t.dtype], t.numel(), self._stream())
+
+    def get_volume_tensor(self, which=VOL_RECON, dtype=None, out=None):
+        out = self._as_output((self.nslice, self.nray, self.nray), dtype, out)
+        self.c("get_volume_device", int(which), ctypes.c_void_p(out.data_ptr()), _torch_dtypes()[out.dtype], out.numel(), self._stream())
+        return out
+
+    def get_projections_tensor(self, which=SINO_B, layout=SINO_PACKED, dtype=None, out=None):
+        out = self._as_output(self._sino_shape(layout), dtype, out)
+        self.c("get_sinogram_device", int(which), ctypes.c_void_p(out.data_ptr()), _torch_dtypes()[out.dtype], int(layout), out.numel(), self._stream())
+        return out
+
     # ---- multimodal (ChemicalTomo) element-wise steps across two engines (include/tomo_hip.h: tomo_mm_*) ----
     def share_stream_with(self, other):
         st = ctypes.c_void_p()
@@ -359,6 +435,41 @@ class _GroupBackend:
 
     def c_get_volume(self, which, ptr):
         self._rows("get_volume", which, ptr, self.nray * self.nray * 4)
+
+    # tensors: every sub-slab takes its rows as a leading-axis view (the pointer offset of _rows), checked once for the whole slab
+    def _split_in(self, t):
+        _on_device(t, self.device)
+        if t.shape[0] != self.nslice:
+            raise ValueError(f"tensor must have {self.nslice} slices, got {t.shape[0]}")
+        if t.dtype not in _torch_dtypes():
+            import torch
+            t = t.to(torch.float32)
+        t = t.contiguous()
+        return [(kid, t[first:first + cnt]) for (first, cnt), kid in zip(self.parts, self.kids)]
+
+    def _split_out(self, shape, dtype, out):
+        out = _SlabBackend._as_output(self, shape, dtype, out)
+        return out, [(kid, out[first:first + cnt]) for (first, cnt), kid in zip(self.parts, self.kids)]
+
+    def set_tilt_series_tensor(self, t, layout=SINO_PACKED, which=SINO_B):
+        for kid, rows in self._split_in(t):
+            kid.set_tilt_series_tensor(rows, layout, which)
+
+    def set_volume_tensor(self, t, which=VOL_RECON):
+        for kid, rows in self._split_in(t):
+            kid.set_volume_tensor(rows, which)
+
+    def get_volume_tensor(self, which=VOL_RECON, dtype=None, out=None):
+        out, parts = self._split_out((self.nslice, self.nray, self.nray), dtype, out)
+        for kid, rows in parts:
+            kid.get_volume_tensor(which, out=rows)
+        return out
+
+    def get_projections_tensor(self, which=SINO_B, layout=SINO_PACKED, dtype=None, out=None):
+        out, parts = self._split_out(_SlabBackend._sino_shape(self, layout), dtype, out)
+        for kid, rows in parts:
+            kid.get_projections_tensor(which, layout, out=rows)
+        return out
 
     def c_set_slice(self, vol, s, ptr):
         kid, ls = self._owner(s)
@@ -574,6 +685,32 @@ class _EngineBase:
             raise ValueError(f"tilt series must have shape {(self.Nslice_, self.Nrow)}, got {b.shape}")
         loc = _f32c(b[self.first:self.first + self.nloc])
         self.be.c("set_tilt_series", _ptr(loc))
+
+    # ---- the same as torch tensors on the engine's device: no host copy, no host wait ------------------------------------
+    def _local_rows(self, t):
+        """This engine's rows [first, first + nloc) of a tensor over all Nslice slices: a leading-axis view, no copy."""
+        _on_device(t, self.gpuID)
+        if t.shape[0] != self.Nslice_:
+            raise ValueError(f"tensor must have {self.Nslice_} slices, got {t.shape[0]}")
+        return t[self.first:self.first + self.nloc]
+
+    def set_tilt_series_tensor(self, t, layout=SINO_PACKED):
+        """The tilt series as a device tensor: (Nslice, Nray*Nproj) with index angle*Nray+ray (``SINO_PACKED``, what ``set_tilt_series``
+        takes) or (Nslice, Nray, Nproj) (``SINO_PUBLIC``, what ``TomoGPU`` is given: the pack happens inside the kernel)."""
+        self.be.set_tilt_series_tensor(self._local_rows(t), layout)
+
+    def set_volume_tensor(self, t, which=VOL_RECON):
+        """(Nslice, Ny, Nz) device tensor -> volume ``which``."""
+        self.be.set_volume_tensor(self._local_rows(t), which)
+
+    def get_volume_tensor(self, which=VOL_RECON, dtype=None, out=None):
+        """This engine's slab of volume ``which`` as a (nloc, Ny, Nz) tensor on its device (float32 by default).  Never a collective:
+        a sharded engine returns its LOCAL slices (``get_volume`` gathers)."""
+        return self.be.get_volume_tensor(which, dtype=dtype, out=out)
+
+    def get_projections_tensor(self, which=SINO_B, layout=SINO_PACKED, dtype=None, out=None):
+        """This engine's slab of sinogram ``which`` (``SINO_B``: the tilt series, ``SINO_G``: the model's projections) as a device tensor."""
+        return self.be.get_projections_tensor(which, layout, dtype=dtype, out=out)
 
     def _owner(self, s):
         if s < 0 or s >= self.Nslice_:

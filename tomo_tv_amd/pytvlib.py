@@ -113,3 +113,13 @@ def pack_tilt_series(tiltSeries):
 
 def load_exp_tilt_series(tomo, tiltSeries):
     tomo.set_tilt_series(pack_tilt_series(tiltSeries))
+
+
+def load_tilt_series_tensor(tomo, tiltSeries):
+    """``load_exp_tilt_series`` for a (Nslice, Nray, Nangles) torch tensor on the engine's device: the pack of ``pack_tilt_series``
+    happens inside the kernel that converts the layout (``SINO_PUBLIC``), nothing crosses the host."""
+    from ._lib import SINO_PUBLIC
+    if not hasattr(tomo, "set_tilt_series_tensor"):
+        raise NotImplementedError("a device tensor needs an engine on the tensor's device (TomoGPU(..., gpu_id=...)); the in-process "
+                                  "multi-GPU engine takes numpy arrays")
+    tomo.set_tilt_series_tensor(tiltSeries, SINO_PUBLIC)

@@ -8,8 +8,21 @@ to the semantics of their canonical loops:
 import numpy as np
 
 from . import _lib, pytvlib
-from ._lib import S_DD, S_DIFF2, VOL_RECON, VOL_YK
-from .engine import multigpuengine, tomoengine
+from ._lib import S_DD, S_DIFF2, SINO_B, SINO_PUBLIC, VOL_RECON, VOL_YK
+from .engine import is_tensor, multigpuengine, tomoengine
+
+
+def _device_tensor(a):
+    """``a`` as a torch tensor if it is one or exports DLPack from a GPU (``torch.from_dlpack`` takes it without a copy); None for
+    numpy arrays and everything else that lives on the host, which keep the host path."""
+    if isinstance(a, np.ndarray):
+        return None
+    if not is_tensor(a):
+        if not hasattr(a, "__dlpack_device__") or a.__dlpack_device__()[0] == 1:      # 1 = kDLCPU
+            return None
+        import torch
+        a = torch.from_dlpack(a)
+    return a if a.is_cuda else None
 
 
 def device_count():
@@ -72,13 +85,20 @@ def _on_rank_threads(fn):
 class TomoGPU:
 
     def __init__(self, tiltAngles, tiltSeries=None, gpu_id=-1, verbose=False, sub_slabs=1):
-        """tiltAngles in degrees, tiltSeries (Nslice, Nray, Nangles) with axis 0 = tilt axis.  ``sub_slabs=K`` (an extension,
+        """tiltAngles in degrees, tiltSeries (Nslice, Nray, Nangles) with axis 0 = tilt axis: a numpy array, or a torch tensor on the
+        GPU (or any object ``torch.from_dlpack`` takes from one), which is handed to the engine without a host copy; with no
+        ``gpu_id`` named and no process group the engine is then built on the tensor's device.  ``sub_slabs=K`` (an extension,
         single GPU): run the volume as K sub-slab engines side by side on the GPU (engine.py: ``_GroupBackend``)."""
         pytvlib.check_hip()
         tiltAngles = np.asarray(tiltAngles, dtype=np.float64)
         self.Nslice, self.Nray, self.Nangles = tiltSeries.shape
         if tiltAngles.size != self.Nangles:
             raise ValueError("tiltAngles and tiltSeries disagree on the number of projections")
+        t = _device_tensor(tiltSeries)
+        if t is not None and gpu_id < 0:
+            from .inprocess import process_group_world
+            if process_group_world() == 1:
+                gpu_id = t.device.index
         config = determine_gpu_config(gpu_id)
         if config == "singleconfig":
             self.tomo = tomoengine(self.Nslice, self.Nray, np.deg2rad(tiltAngles), device=max(gpu_id, 0), sub_slabs=sub_slabs)
@@ -92,7 +112,11 @@ class TomoGPU:
     def set_tilt_series(self, tiltSeries):
         self.Nslice, self.Nray, self.Nangles = tiltSeries.shape
         self.recon = None
-        self.tomo.set_tilt_series(pytvlib.pack_tilt_series(tiltSeries))
+        t = _device_tensor(tiltSeries)
+        if t is None:
+            self.tomo.set_tilt_series(pytvlib.pack_tilt_series(tiltSeries))
+        else:
+            pytvlib.load_tilt_series_tensor(self.tomo, t)
 
     # ---- drivers (gpu/reconstructor.py:61-192) ---------------------------------------------------------
     @_on_rank_threads
@@ -240,7 +264,24 @@ class TomoGPU:
             collect(dPOCS)
         return self.dd_vec, self.tv_vec
 
-    def get_recon(self):
-        """(Nslice, Nray, Nray) float64 like the reference (gpu/reconstructor.py:207-215)."""
+    def _tensor_engine(self):
+        if not hasattr(self.tomo, "get_volume_tensor") or getattr(self.tomo, "comm", None) is not None:
+            raise NotImplementedError("as_tensor needs the whole volume on one device: a sharded engine hands out its local slab "
+                                      "(tomo.get_volume_tensor), the gathering calls return numpy")
+        return self.tomo
+
+    def get_recon(self, as_tensor=False, dtype=None):
+        """(Nslice, Nray, Nray) float64 like the reference (gpu/reconstructor.py:207-215).  ``as_tensor=True``: a torch tensor on the
+        engine's device instead (``dtype`` torch.float32 by default, or torch.float64), converted on the device, no host copy."""
+        if as_tensor:
+            return self._tensor_engine().get_volume_tensor(VOL_RECON, dtype=dtype)
         self.recon = self.tomo.get_volume(VOL_RECON).astype(np.float64)
         return self.recon
+
+    def get_projections(self, as_tensor=False, dtype=None):
+        """The tilt series the engine holds, (Nslice, Nray, Nangles) as it was given (the reference's stub: gpu/reconstructor.py:217):
+        numpy float32, or with ``as_tensor=True`` a torch tensor on the engine's device."""
+        if as_tensor:
+            return self._tensor_engine().get_projections_tensor(SINO_B, SINO_PUBLIC, dtype=dtype)
+        b = self.tomo.get_projections()
+        return np.ascontiguousarray(b.reshape(self.Nslice, self.Nangles, self.Nray).transpose(0, 2, 1))
