@@ -181,6 +181,25 @@ int tomo_sino_diff_norm_sq(tomo_engine *e, int a, int b, int slot);     /* multi
 int tomo_sino_proj_max(tomo_engine *e, int sino, float *out_host);      /* multimodal.cpp:323-327: max per projection */
 int tomo_sino_proj_scale(tomo_engine *e, int sino, const float *div_host, const float *mul_host); /* b <- b/div[p]*mul[p] */
 int tomo_l1_norm(tomo_engine *e, int vol);                              /* :436 l1_norm -> TOMO_S_L1 */
+
+/* ---- tilt-series alignment ------------------------------------------------------------------------------------------------
+ * The reference aligns on the host, one image at a time, by the centre of mass (cpu/utils/logger.py:237-252: integer roll so that
+ * the centre of mass lands on size // 2); these three calls do that on the resident series and add what projection matching
+ * needs.  Projection a of a sinogram slot is the image X_a[r][s], ray r in [0, Nray), slice s in [0, Nslice).  A shift (dr, ds)
+ * moves content by +d: dst_a[r][s] = src_a(r - dr, s - ds), the sense of np.roll.  One whole-volume engine only: an engine bound
+ * to a communicator returns TOMO_ERR_STATE.  All three wait for their result; results are bit-identical from run to run.
+ *   tomo_sino_moments: out_host[a] = {sum X_a, sum r X_a, sum s X_a} over the real samples, in binary64.
+ *   tomo_sino_xcorr:   out_host[a][u + S][v + S] = sum_{r,s} (A_a[r][s] - mA_a)(B_a[r + u][s + v] - mB_a), S = max_shift, over the
+ *       (r, s) with both samples inside the image; mA, mB the per-angle means (0 with subtract_mean = 0).  1 <= S <= 16 and
+ *       S <= min(Nray, Nslice) - 1.  Not divided by the overlap: the entry at (u, v) sums (Nray - |u|)(Nslice - |v|) products, which
+ *       leans the peak towards zero shift by the factor (1 - |u|/Nray)(1 - |v|/Nslice) -- 3 % per axis at S = 16, Nray = 512, large
+ *       for stacks only a few S thin -- exactly like the FFT correlation of zero-padded images.
+ *   tomo_sino_shift:   bilinear resampling by shifts_host[a] = {dr, ds}; samples outside the image are 0, or wrap around (wrap = 1).
+ *       A whole-pixel shift reproduces the source bits; a shift beyond the image without wrap gives zeros.  src != dst.
+ * TOMO_ERR_ARG: bad slot, src == dst, max_shift out of range, a null pointer, a non-finite shift. */
+int tomo_sino_moments(tomo_engine *e, int sino, double *out_host);      /* [Nproj][3]   logger.py:237-247 */
+int tomo_sino_xcorr(tomo_engine *e, int sino_a, int sino_b, int max_shift, int subtract_mean, double *out_host); /* [Nproj][2S+1][2S+1] */
+int tomo_sino_shift(tomo_engine *e, int src, int dst, const float *shifts_host, int wrap);   /* logger.py:249-250 */
 int tomo_read_scalars(tomo_engine *e, double *out, int count);          /* synchronises the stream */
 /* the same without a pipeline bubble: _snapshot enqueues the copy of all slots behind the kernels that produce them (and behind
  * an evaluation in flight on the second stream) and returns; _read waits for that copy only.  The ASD-POCS drivers enqueue the

@@ -117,6 +117,9 @@ SIGNATURES = {
     "tomo_sino_diff_norm_sq": [_p, _i, _i, _i],
     "tomo_sino_proj_max": [_p, _i, _p],
     "tomo_sino_proj_scale": [_p, _i, _p, _p],
+    "tomo_sino_moments": [_p, _i, _p],
+    "tomo_sino_xcorr": [_p, _i, _i, _i, _i, _p],
+    "tomo_sino_shift": [_p, _i, _i, _p, _i],
     "tomo_fgp_begin_vol": [_p, _i],
     "tomo_tv_fgp_vol": [_p, _i, _i, _f],
     "tomo_bind_fgp_halo": [_p, _p, _p, _p, _p],

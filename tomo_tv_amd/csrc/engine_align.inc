@@ -1,0 +1,117 @@
+// engine_align.inc -- tilt-series alignment: per-angle moments, windowed cross-correlation, resampling by per-angle shifts.
+// Part of tomo_engine.hip (included inside its extern "C" block, after engine_api.inc); kernels: kernels_align.hip.h.
+//
+// One whole-volume engine only: a shift along the tilt axis moves samples across slab boundaries, so an engine bound to a
+// communicator refuses (TOMO_ERR_STATE).  The buffers (partial sums, moments, means, the window) belong to the engine's registry and
+// are kept: after the first call of a given size nothing is allocated.
+
+static int al_ensure(tomo_engine *e, void **p, size_t *have, size_t bytes)
+{
+    if (*have >= bytes) return TOMO_OK;
+    if (*p) { HIPCHK(hipStreamSynchronize(e->stream)); e->pool.release(*p); *p = nullptr; *have = 0; }
+    if (int rc = dev_alloc(e, ENGINE, p, bytes, false)) return rc;
+    *have = bytes;
+    return TOMO_OK;
+}
+
+#define NEED_ALIGN(e) do { NEED(e); if ((e)->comm) return fail(TOMO_ERR_STATE, "alignment runs on one whole-volume engine: this engine has a communicator"); } while (0)
+
+// moments of sinogram g into al_mom[which] ([np][3] doubles) and its means into al_mean[which] ([np] floats); enqueued, no wait
+static int al_moments(tomo_engine *e, const float *g, int which)
+{
+    const int nblk = (e->n + AL_MROWS - 1) / AL_MROWS;
+    int rc;
+    if ((rc = al_ensure(e, (void **)&e->al_part, &e->al_part_bytes, (size_t)e->np * nblk * 3 * sizeof(double)))) return rc;
+    if (!e->al_mom) { if ((rc = dev_alloc(e, GEOMETRY, (void **)&e->al_mom, (size_t)2 * e->np * 3 * sizeof(double), false))) return rc; }
+    if (!e->al_mean) { if ((rc = dev_alloc(e, GEOMETRY, (void **)&e->al_mean, (size_t)2 * e->np * sizeof(float), false))) return rc; }
+    hipLaunchKernelGGL(k_sino_moments, dim3(nblk, e->np), dim3(256), 0, e->stream, g, e->al_part, e->n, e->nx, e->sx);
+    LAUNCHCHK();
+    hipLaunchKernelGGL(k_sino_moments_finish, dim3((e->np * 3 + 255) / 256), dim3(256), 0, e->stream, (const double *)e->al_part,
+                       e->al_mom + (size_t)which * e->np * 3, e->al_mean + (size_t)which * e->np, e->np, nblk, (double)e->n * (double)e->nx);
+    LAUNCHCHK();
+    return TOMO_OK;
+}
+
+int tomo_sino_moments(tomo_engine *e, int sino, double *out_host)
+{
+    NEED_ALIGN(e);
+    if (!out_host) return fail(TOMO_ERR_ARG, "null output");
+    { int rc_ = order_after_async(e); if (rc_) return rc_; }
+    float *g; int rc;
+    if ((rc = sino_slot(e, sino, &g)) || (rc = al_moments(e, g, 0))) return rc;
+    HIPCHK(hipMemcpyAsync(out_host, e->al_mom, (size_t)e->np * 3 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return TOMO_OK;
+}
+
+int tomo_sino_xcorr(tomo_engine *e, int sino_a, int sino_b, int max_shift, int subtract_mean, double *out_host)
+{
+    NEED_ALIGN(e);
+    if (!out_host) return fail(TOMO_ERR_ARG, "null output");
+    const int S = max_shift;
+    if (S < 1 || S > 16 || S > std::min(e->n, e->nx) - 1) return fail(TOMO_ERR_ARG, "max_shift must be 1..16 and at most min(Nray, Nslice) - 1");
+    { int rc_ = order_after_async(e); if (rc_) return rc_; }
+    float *A, *B; int rc;
+    if ((rc = sino_slot(e, sino_a, &A)) || (rc = sino_slot(e, sino_b, &B))) return rc;
+    const float *mA = nullptr, *mB = nullptr;
+    if (subtract_mean) {
+        if ((rc = al_moments(e, A, 0)) || (rc = al_moments(e, B, 1))) return rc;
+        mA = e->al_mean; mB = e->al_mean + e->np;
+    }
+    const int smax = S <= 4 ? 4 : (S <= 8 ? 8 : 16), wm = 2 * smax + 1, w = 2 * S + 1;
+    const int nchunk = (e->nx + 63) / 64, ncg = (nchunk + AL_KC - 1) / AL_KC, nrb = (e->n + AL_R - 1) / AL_R, nblk = nrb * ncg;
+    if ((rc = al_ensure(e, (void **)&e->al_part, &e->al_part_bytes, (size_t)e->np * nblk * wm * wm * sizeof(double)))) return rc;
+    if ((rc = al_ensure(e, (void **)&e->al_out, &e->al_out_bytes, (size_t)e->np * 33 * 33 * sizeof(double)))) return rc;
+    const dim3 grid(ncg, nrb, e->np), block(256);
+    if (smax == 4) hipLaunchKernelGGL((k_sino_xcorr<4, 9, 9>), grid, block, 0, e->stream, A, B, mA, mB, e->al_part, e->n, e->nx, e->sx, nchunk);
+    else if (smax == 8) hipLaunchKernelGGL((k_sino_xcorr<8, 9, 9>), grid, block, 0, e->stream, A, B, mA, mB, e->al_part, e->n, e->nx, e->sx, nchunk);
+    else hipLaunchKernelGGL((k_sino_xcorr<16, 11, 11>), grid, block, 0, e->stream, A, B, mA, mB, e->al_part, e->n, e->nx, e->sx, nchunk);
+    LAUNCHCHK();
+    hipLaunchKernelGGL(k_sino_xcorr_finish, dim3((e->np * w * w + 255) / 256), dim3(256), 0, e->stream, (const double *)e->al_part, e->al_out,
+                       e->np, nblk, smax, S);
+    LAUNCHCHK();
+    HIPCHK(hipMemcpyAsync(out_host, e->al_out, (size_t)e->np * w * w * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return TOMO_OK;
+}
+
+// -d = k + t with k = floor(-d) and t in [0, 1).  k and the binary64 fraction are exact (d is a binary32 number); rounded to binary32
+// the fraction of a tiny positive d (1 - 2^-30, say) becomes 1, which is the whole-pixel shift k + 1 and is passed on as such, so
+// that the kernel's copy path takes it -- never a two-tap form with weights 0 and 1.  Without wrap a k beyond the image on either
+// side is pinned just outside it (every tap is then outside: zeros); with wrap it is taken modulo size.
+static void al_split(float d, int size, int wrap, int *k, float *t)
+{
+    const double nd = -(double)d;
+    double fl = std::floor(nd);
+    *t = (float)(nd - fl);
+    if (*t >= 1.f) { *t = 0.f; fl += 1.0; }
+    if (wrap) { double m = std::fmod(fl, (double)size); if (m < 0) m += size; *k = (int)m; }
+    else *k = (int)std::max(-(double)size - 2.0, std::min((double)size + 2.0, fl));
+}
+
+int tomo_sino_shift(tomo_engine *e, int src, int dst, const float *shifts_host, int wrap)
+{
+    NEED_ALIGN(e);
+    if (!shifts_host) return fail(TOMO_ERR_ARG, "null shifts");
+    if (src == dst) return fail(TOMO_ERR_ARG, "source and destination must be different sinogram slots");
+    for (int i = 0; i < 2 * e->np; ++i) if (!std::isfinite(shifts_host[i])) return fail(TOMO_ERR_ARG, "non-finite shift");
+    { int rc_ = order_after_async(e); if (rc_) return rc_; }
+    float *s, *d; int rc;
+    if ((rc = sino_slot(e, src, &s)) || (rc = sino_slot(e, dst, &d))) return rc;
+    if ((rc = ensure_stage(e, (size_t)e->np * sizeof(int4)))) return rc;
+    std::vector<int4> tab(e->np);
+    for (int a = 0; a < e->np; ++a) {
+        float tr, ts;
+        al_split(shifts_host[2 * a], e->n, wrap, &tab[a].x, &tr);
+        al_split(shifts_host[2 * a + 1], e->nx, wrap, &tab[a].y, &ts);
+        std::memcpy(&tab[a].z, &tr, 4); std::memcpy(&tab[a].w, &ts, 4);
+    }
+    HIPCHK(hipMemcpyAsync(e->stage, tab.data(), (size_t)e->np * sizeof(int4), hipMemcpyHostToDevice, e->stream));
+    const int blocks = (int)std::min<int64_t>(((int64_t)e->n * e->sx + 255) / 256, 1024);
+    const dim3 grid(blocks, e->np), block(256);
+    if (wrap) hipLaunchKernelGGL((k_sino_shift<true>), grid, block, 0, e->stream, (const float *)s, d, (const int4 *)e->stage, e->n, e->nx, e->sx);
+    else hipLaunchKernelGGL((k_sino_shift<false>), grid, block, 0, e->stream, (const float *)s, d, (const int4 *)e->stage, e->n, e->nx, e->sx);
+    LAUNCHCHK();
+    HIPCHK(hipStreamSynchronize(e->stream));        // the table is read from this call's host memory
+    return TOMO_OK;
+}

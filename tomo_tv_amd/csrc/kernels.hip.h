@@ -18,3 +18,4 @@
 #include "kernels_tv.hip.h"       // TV value / gradient / update
 #include "kernels_fgp.hip.h"      // FGP-TV
 #include "kernels_pdhg.hip.h"     // Chambolle-Pock: dual sinogram, fused dual / divergence / primal pass
+#include "kernels_align.hip.h"    // tilt-series alignment: moments, windowed cross-correlation, resampling

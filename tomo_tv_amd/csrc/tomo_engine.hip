@@ -284,6 +284,10 @@ struct tomo_engine {
     float *pdhg_lo = nullptr, *pdhg_hi = nullptr, *pdhg_send_first = nullptr, *pdhg_send_last = nullptr;
     float *stage = nullptr;
     size_t stage_bytes = 0;
+    // alignment (engine_align.inc): the workgroups' partial sums, per-angle moments [2][np][3] and means [2][np], the window read back
+    double *al_part = nullptr, *al_mom = nullptr, *al_out = nullptr;
+    float *al_mean = nullptr;
+    size_t al_part_bytes = 0, al_out_bytes = 0;
     // scalars
     double *d_scal = nullptr, *d_scal_own = nullptr, *d_part = nullptr, *d_part_aux = nullptr, *d_part_tv = nullptr;
     double *h_snap = nullptr;          // pinned: tomo_scalars_snapshot
@@ -508,6 +512,7 @@ extern "C" {
 #include "engine_api.inc"
 #include "engine_tv.inc"
 #include "engine_pdhg.inc"
+#include "engine_align.inc"
 #include "engine_comm.inc"
 #include "engine_options.inc"
 

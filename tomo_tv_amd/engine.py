@@ -421,6 +421,11 @@ class _GroupBackend:
             raise _lib.TomoError(f"tomo_{name} is a per-slab step form: not offered on a sub-slab group")
         self._all(name, *args)           # slice-independent: the same call on every sub-slab
 
+    def _no_align(self, *a):
+        raise NotImplementedError("alignment runs on one whole-volume engine: a shift along the tilt axis crosses the sub-slabs")
+
+    c_sino_moments = c_sino_xcorr = c_sino_shift = _no_align
+
     def c_set_tilt_series(self, ptr):
         self._rows("set_sinogram", SINO_B, ptr, self.nray * self.nproj * 4)
 
@@ -1062,6 +1067,38 @@ class _EngineBase:
         self._pdhg_one_engine()
         self.be.c("pdhg_tv_step" if self.comm is None else "pdhg_slab_tv_step", int(x_vol), int(xbar_vol), int(u_vol), int(p_vol0),
                   float(sigma), float(tau), float(lam), float(theta), int(bool(precond)), int(slot))
+
+    # ---- tilt-series alignment (include/tomo_hip.h: tomo_sino_moments / tomo_sino_xcorr / tomo_sino_shift) -------------------------
+    def _align_one_engine(self):
+        """One whole-volume engine: a shift along the tilt axis crosses slab boundaries, and nothing carries that halo yet."""
+        if self.comm is not None or self.sub_slabs > 1 or not isinstance(self.be, _SlabBackend):
+            raise NotImplementedError("alignment runs on one whole-volume engine (not on slabs sharded over ranks, devices or sub_slabs)")
+
+    def sino_moments(self, which=SINO_B):
+        """(Nproj, 3) float64: sum X, sum r X, sum s X of every projection X[r][s] of sinogram slot ``which`` (r = ray, s = slice)."""
+        self._align_one_engine()
+        out = np.empty((self.Nproj, 3), np.float64)
+        self.be.c("sino_moments", int(which), _ptr(out))
+        return out
+
+    def sino_xcorr(self, a, b, max_shift, subtract_mean=True):
+        """(Nproj, 2S+1, 2S+1) float64, S = ``max_shift``: C[p][u+S][v+S] = sum_{r,s} (A_p[r][s] - mA_p)(B_p[r+u][s+v] - mB_p) over the
+        samples inside both images of sinogram slots ``a`` and ``b`` (u along rays, v along slices); not normalised by the overlap.
+        B = A shifted by +d peaks at (u, v) = d."""
+        self._align_one_engine()
+        S = int(max_shift)
+        out = np.empty((self.Nproj, 2 * S + 1, 2 * S + 1), np.float64)
+        self.be.c("sino_xcorr", int(a), int(b), S, int(bool(subtract_mean)), _ptr(out))
+        return out
+
+    def sino_shift(self, src, dst, shifts, wrap=False):
+        """dst_p[r][s] = src_p(r - dr_p, s - ds_p), bilinear, ``shifts`` = (Nproj, 2) of (dr, ds): the sense of ``np.roll``.  Outside the
+        image: zeros, or with ``wrap`` the image repeated (exactly ``np.roll`` for whole-pixel shifts).  ``src`` != ``dst``."""
+        self._align_one_engine()
+        sh = np.ascontiguousarray(shifts, dtype=np.float32)
+        if sh.shape != (self.Nproj, 2):
+            raise ValueError(f"shifts must have shape {(self.Nproj, 2)}, got {sh.shape}")
+        self.be.c("sino_shift", int(src), int(dst), _ptr(sh), int(bool(wrap)))
 
     def synchronize(self):
         self.be.c("synchronize")

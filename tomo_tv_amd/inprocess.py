@@ -245,6 +245,12 @@ class InProcessMultiGPU:
     def __dir__(self):
         return sorted(set(dir(type(self)) + dir(self._engines[0])))
 
+    # alignment shifts the series along the tilt axis, across the devices' slabs: not offered here (engine.py: _align_one_engine)
+    def _no_align(self, *args, **kw):
+        raise NotImplementedError("alignment runs on one whole-volume engine, not on slabs spread over devices")
+
+    sino_moments = sino_xcorr = sino_shift = _align_one_engine = _no_align
+
     # the reference's own multi-GPU queries (multigpuengine.cpp:385-421)
     def get_gpu_ids(self):
         return list(self._devices)

@@ -7,8 +7,8 @@ to the semantics of their canonical loops:
 """
 import numpy as np
 
-from . import _lib, pytvlib
-from ._lib import S_DD, S_DIFF2, SINO_B, SINO_PUBLIC, VOL_RECON, VOL_YK
+from . import _lib, align, pytvlib
+from ._lib import S_DD, S_DIFF2, SINO_B, SINO_G, SINO_PUBLIC, SINO_USER0, VOL_RECON, VOL_YK
 from .engine import is_tensor, multigpuengine, tomoengine
 
 
@@ -112,6 +112,7 @@ class TomoGPU:
     def set_tilt_series(self, tiltSeries):
         self.Nslice, self.Nray, self.Nangles = tiltSeries.shape
         self.recon = None
+        self._align_kept, self._align_shifts = False, None      # a new series: nothing kept, nothing applied
         t = _device_tensor(tiltSeries)
         if t is None:
             self.tomo.set_tilt_series(pytvlib.pack_tilt_series(tiltSeries))
@@ -263,6 +264,113 @@ class TomoGPU:
         if pending is not None:
             collect(dPOCS)
         return self.dd_vec, self.tv_vec
+
+    # ---- alignment of the tilt series (an extension: the reference centres by mass on the host, cpu/utils/logger.py:237-252) ----
+    ALIGN_SLOT = SINO_USER0          # sinogram slot that keeps the series as it was given
+    ALIGN_MODEL_SLOT = SINO_USER0 + 39   # the last user slot: the leave-one-out model projections (refine_alignment)
+
+    def _align_engine(self):
+        t = self.tomo
+        if not hasattr(t, "_align_one_engine"):
+            raise NotImplementedError("alignment runs on one whole-volume engine")
+        t._align_one_engine()
+        if not self._align_kept:
+            # the series as given, kept on the device: every later shift resamples THIS copy, so interpolation never compounds
+            # (a whole-pixel shift of zero copies bit for bit).  Only set_tilt_series of THIS object drops the copy: a caller that
+            # replaces the series through self.tomo directly must call set_tilt_series instead, or the old series is resampled
+            t.sino_shift(SINO_B, self.ALIGN_SLOT, np.zeros((self.Nangles, 2), np.float32))
+            self._align_kept = True
+        return t
+
+    def get_alignment(self):
+        """Total shifts (Nangles, 2) of (dr, ds) -- along the rays, along the tilt axis -- applied to the series as it was given."""
+        return np.zeros((self.Nangles, 2)) if self._align_shifts is None else np.array(self._align_shifts, np.float64)
+
+    def set_alignment(self, shifts, wrap=False):
+        """Apply total shifts to the series as it was given (not on top of earlier ones): projection a moves by (dr, ds) =
+        ``shifts[a]`` in the sense of ``np.roll``, bilinear for fractions, zeros (or with ``wrap`` the other edge) moving in."""
+        t = self._align_engine()
+        shifts = np.array(shifts, np.float64).reshape(self.Nangles, 2)
+        t.sino_shift(self.ALIGN_SLOT, SINO_B, shifts, wrap=wrap)
+        self._align_shifts = shifts
+        return self.get_alignment()
+
+    def align_center_of_mass(self):
+        """The reference's rule per projection (cpu/utils/logger.py:237-252): roll, with wrap-around, so that the integer-truncated
+        centre of mass lands on ``size // 2`` of both axes.  Replaces the engine's tilt series; returns the (Nangles, 2) integer
+        shifts (dr, ds)."""
+        t = self._align_engine()
+        shifts = align.center_of_mass_shifts(t.sino_moments(self.ALIGN_SLOT), self.Nray, self.Nslice)
+        self.set_alignment(shifts, wrap=True)
+        return shifts
+
+    def _model_leave_one_out(self, niter):
+        """Into sinogram slot ``ALIGN_MODEL_SLOT``: for every projection a, projection a of a SIRT reconstruction (``niter`` iterations
+        from zero) that never saw projection a.  One engine does it: before every SIRT step the data of projection a are replaced by
+        the model's own projection a, so that its residual is zero and only the other projections shape the volume.  The series goes
+        through torch tensors on the engine's device (plumbing: two sinogram copies per step); B is put back as it was."""
+        t = self.tomo
+        pytvlib.initialize_algorithm(t, "SIRT")
+        b = t.get_projections_tensor(SINO_B, SINO_PUBLIC)
+        work, model = b.clone(), b.clone()
+        for a in range(self.Nangles):
+            work.copy_(b)
+            t.set_tilt_series_tensor(work, SINO_PUBLIC)
+            t.restart_recon()
+            for _ in range(int(niter)):
+                t.forward_projection()
+                work[:, :, a] = t.get_projections_tensor(SINO_G, SINO_PUBLIC)[:, :, a]
+                t.set_tilt_series_tensor(work, SINO_PUBLIC)
+                t.SIRT(1)
+            t.forward_projection()
+            model[:, :, a] = t.get_projections_tensor(SINO_G, SINO_PUBLIC)[:, :, a]
+        t.set_tilt_series_tensor(b, SINO_PUBLIC)
+        t.be.set_tilt_series_tensor(model, SINO_PUBLIC, self.ALIGN_MODEL_SLOT)
+        return self.ALIGN_MODEL_SLOT
+
+    def refine_alignment(self, Nouter=5, max_shift=8, recon=None, subpixel=True, leave_one_out=False, loo_iters=20):
+        """Projection matching.  Every outer pass reconstructs (``recon(self)``; default 20 SIRT iterations), projects the result,
+        correlates each model projection with the measured one over shifts in [-max_shift, max_shift]^2 (``sino_xcorr``), moves the
+        total shift of every projection against the peak it found and resamples the series AS GIVEN by the new totals (zeros move
+        in).  The mean of ds -- a translation of the volume along the tilt axis, which no projection can see -- is removed; without
+        ``subpixel`` peaks and the removed mean are whole pixels, so the series is only ever copied, never interpolated.  The
+        translation of the volume across the tilt axis (dr_a = x cos(theta_a) + y sin(theta_a)) is left where the data put it.
+        A peak on the window's border keeps its integer position and is flagged in ``self.align_at_border`` (per pass, per angle):
+        raise ``max_shift`` or pre-align by ``align_center_of_mass``.  Returns the total (Nangles, 2) shifts; ``self.align_history``
+        holds them after every pass, ``self.align_peaks`` the peaks and ``self.align_int_peaks`` the whole-pixel maxima they refine.
+        The series as given is kept in sinogram slot ``ALIGN_SLOT`` from the first alignment call on and dropped only by
+        ``set_tilt_series`` of this object: replace the series through it, not through ``self.tomo``.
+
+        ``leave_one_out``: the model of projection a comes from a SIRT reconstruction (``loo_iters`` iterations, ``recon`` is not used)
+        that never saw projection a.  With few projections the plain form stalls -- the reconstruction reproduces every measured
+        projection where it lies, so its model correlates best at zero shift (at 9 projections of 32 x 32 slices no peak leaves
+        (0, 0)) -- and this form does not; it costs ``Nangles`` reconstructions per pass and needs torch."""
+        t = self._align_engine()
+        if leave_one_out and recon is not None:
+            raise ValueError("leave_one_out reconstructs by itself (loo_iters SIRT iterations): recon is not used")
+        if recon is None:
+            recon = lambda rec: rec.sirt(20, show_convergence=False)  # noqa: E731
+        shifts = self.get_alignment()
+        self.align_history, self.align_at_border, self.align_peaks, self.align_int_peaks = [], [], [], []
+        for _ in range(int(Nouter)):
+            if leave_one_out:
+                model = self._model_leave_one_out(loo_iters)
+            else:
+                recon(self)
+                t.forward_projection()
+                model = SINO_G
+            C = t.sino_xcorr(model, SINO_B, int(max_shift))
+            peaks, border = align.find_peaks(C, subpixel)
+            self.align_int_peaks.append(peaks if not subpixel else align.find_peaks(C, False)[0])
+            shifts = shifts - peaks
+            m = shifts[:, 1].mean()
+            shifts[:, 1] -= m if subpixel else np.round(m)
+            t.sino_shift(self.ALIGN_SLOT, SINO_B, shifts, wrap=False)
+            self._align_shifts = shifts.copy()
+            self.align_peaks.append(peaks)
+            self.align_history.append(shifts.copy())
+            self.align_at_border.append(border)
+        return self.get_alignment()
 
     def _tensor_engine(self):
         if not hasattr(self.tomo, "get_volume_tensor") or getattr(self.tomo, "comm", None) is not None:
