@@ -184,8 +184,8 @@ int tomo_l1_norm(tomo_engine *e, int vol);                              /* :436 
 
 /* ---- tilt-series alignment ------------------------------------------------------------------------------------------------
  * The reference aligns on the host, one image at a time, by the centre of mass (cpu/utils/logger.py:237-252: integer roll so that
- * the centre of mass lands on size // 2); these three calls do that on the resident series and add what projection matching
- * needs.  Projection a of a sinogram slot is the image X_a[r][s], ray r in [0, Nray), slice s in [0, Nslice).  A shift (dr, ds)
+ * the centre of mass lands on size // 2); the first three calls do that on the resident series and add what projection matching
+ * needs, the last two take out an in-plane rotation (a tilt axis that does not run along the detector columns).  Projection a of a sinogram slot is the image X_a[r][s], ray r in [0, Nray), slice s in [0, Nslice).  A shift (dr, ds)
  * moves content by +d: dst_a[r][s] = src_a(r - dr, s - ds), the sense of np.roll.  One whole-volume engine only: an engine bound
  * to a communicator returns TOMO_ERR_STATE.  All three wait for their result; results are bit-identical from run to run.
  *   tomo_sino_moments: out_host[a] = {sum X_a, sum r X_a, sum s X_a} over the real samples, in binary64.
@@ -196,10 +196,22 @@ int tomo_l1_norm(tomo_engine *e, int vol);                              /* :436 
  *       for stacks only a few S thin -- exactly like the FFT correlation of zero-padded images.
  *   tomo_sino_shift:   bilinear resampling by shifts_host[a] = {dr, ds}; samples outside the image are 0, or wrap around (wrap = 1).
  *       A whole-pixel shift reproduces the source bits; a shift beyond the image without wrap gives zeros.  src != dst.
- * TOMO_ERR_ARG: bad slot, src == dst, max_shift out of range, a null pointer, a non-finite shift. */
+ *   tomo_sino_affine:  dst_a[r][s] = bilinear(src_a)(r', s') with r' = m00 r + m01 s + m02, s' = m10 r + m11 s + m12 and
+ *       m_host[a] = {m00, m01, m02, m10, m11, m12} in binary64: the map from a destination sample to its source position (in-plane
+ *       rotation about any centre, magnification and shift in ONE interpolation).  Taps outside [0, Nray) x [0, Nslice) are 0; there
+ *       is no wrap form.  The coordinates are evaluated in binary64, fma(m00, r, fma(m01, s, m02)), and split there into floor and
+ *       fraction; only the fraction is rounded to binary32, and a zero fraction drops its tap.  Hence: an identity matrix copies the
+ *       source bits; a pure translation {1, 0, -dr, 0, 1, -ds} gives the bits of tomo_sino_shift(wrap = 0) for the same (binary32)
+ *       shift, fractions included; a whole-pixel map (quarter turns, flips) copies samples, and an Inf next to a copied sample never
+ *       becomes NaN.  src != dst.
+ *   tomo_sino_axis_profile: out_host[a][s] = sum_r X_a[r][s], in binary64 from the first sample, added in a fixed order.  For a
+ *       parallel-beam series whose tilt axis runs along s this mass of slice s is the same in every projection a.
+ * TOMO_ERR_ARG: bad slot, src == dst, max_shift out of range, a null pointer, a non-finite shift or matrix entry. */
 int tomo_sino_moments(tomo_engine *e, int sino, double *out_host);      /* [Nproj][3]   logger.py:237-247 */
 int tomo_sino_xcorr(tomo_engine *e, int sino_a, int sino_b, int max_shift, int subtract_mean, double *out_host); /* [Nproj][2S+1][2S+1] */
 int tomo_sino_shift(tomo_engine *e, int src, int dst, const float *shifts_host, int wrap);   /* logger.py:249-250 */
+int tomo_sino_affine(tomo_engine *e, int src, int dst, const double *m_host);                /* [Nproj][6] */
+int tomo_sino_axis_profile(tomo_engine *e, int sino, double *out_host);                      /* [Nproj][Nslice] */
 int tomo_read_scalars(tomo_engine *e, double *out, int count);          /* synchronises the stream */
 /* the same without a pipeline bubble: _snapshot enqueues the copy of all slots behind the kernels that produce them (and behind
  * an evaluation in flight on the second stream) and returns; _read waits for that copy only.  The ASD-POCS drivers enqueue the

@@ -1,7 +1,9 @@
-"""Host side of the tilt-series alignment: the peak rule of projection matching and the centre-of-mass rule of the reference.
+"""Host side of the tilt-series alignment: the peak rule of projection matching, the centre-of-mass rule of the reference, the
+matrices of the affine resampling and the score and minimum rule of the tilt-axis estimate.
 
-The windows are ``Nangles * (2S+1)^2`` doubles, so this is bookkeeping, not hot path: the correlation itself, the moments and the
-resampling are HIP kernels (``tomoengine.sino_xcorr`` / ``sino_moments`` / ``sino_shift``)."""
+The windows are ``Nangles * (2S+1)^2`` doubles, the matrices ``Nangles * 6`` and the profiles ``Nangles * Nslice``, so this is
+bookkeeping, not hot path: the correlation itself, the moments, the profiles and the resampling are HIP kernels
+(``tomoengine.sino_xcorr`` / ``sino_moments`` / ``sino_axis_profile`` / ``sino_shift`` / ``sino_affine``)."""
 import numpy as np
 
 
@@ -32,6 +34,77 @@ def find_peaks(C, subpixel=True):
             dv = _parabola(C[a, iu, iv - 1], C[a, iu, iv], C[a, iu, iv + 1])
         peaks[a] = (iu - S + du, iv - S + dv)
     return peaks, border
+
+
+def _cos_sin_deg(deg):
+    """cos and sin of an angle in degrees; at multiples of 90 the exact 0 and +-1, never the output of cos or sin"""
+    q = float(deg) % 360.0
+    if q % 90.0 == 0.0:
+        return ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(q // 90.0)]
+    t = np.deg2rad(float(deg))
+    return float(np.cos(t)), float(np.sin(t))
+
+
+def affine_matrices(shifts, rotation_deg, magnification, N, Nslice):
+    """(Nproj, 6) float64 for ``tomoengine.sino_affine``: per projection the content is rotated by ``+rotation_deg`` about the image
+    centre c = ((N-1)/2, (Nslice-1)/2), counter-clockwise from the r axis towards the s axis (a sample on the +r side of the centre
+    moves towards +s), then scaled by ``magnification`` about c, then moved by ``+shift`` = (dr, ds) in ``np.roll``'s sense.  The row
+    (m00, m01, m02, m10, m11, m12) is the inverse map, from a destination sample to its source position:
+    ``src = R(-phi) / mag . (dst - c - d) + c``.  ``rotation_deg`` and ``magnification`` may be scalars (the same for every projection)
+    or one value per projection.  Rotation 0 with magnification 1 gives the exact translation (1, 0, -dr, 0, 1, -ds), and a rotation by
+    a multiple of 90 degrees takes cos and sin as exact 0 and +-1 (a quarter turn of a square image then maps samples onto samples)."""
+    d = np.asarray(shifts, np.float64).reshape(-1, 2)
+    P = d.shape[0]
+    rot = np.broadcast_to(np.asarray(rotation_deg, np.float64), (P,))
+    mag = np.broadcast_to(np.asarray(magnification, np.float64), (P,))
+    if not np.all(np.isfinite(mag)) or np.any(mag <= 0.0):
+        raise ValueError("magnification must be positive and finite")
+    cr, cs = 0.5 * (N - 1), 0.5 * (Nslice - 1)
+    M = np.zeros((P, 6))
+    for a in range(P):
+        if rot[a] % 360.0 == 0.0 and mag[a] == 1.0:
+            M[a] = (1.0, 0.0, -d[a, 0], 0.0, 1.0, -d[a, 1])
+            continue
+        c, s = _cos_sin_deg(rot[a])
+        m00, m01, m10, m11 = c / mag[a], s / mag[a], -s / mag[a], c / mag[a]
+        pr, ps = cr + d[a, 0], cs + d[a, 1]
+        M[a] = (m00, m01, cr - (m00 * pr + m01 * ps), m10, m11, cs - (m10 * pr + m11 * ps))
+    return M
+
+
+def axis_score_border(N, search_deg):
+    """H = ceil(N/2 sin(search_deg)): a rotation by up to ``search_deg`` about the centre moves a sample of a row of N rays by at most
+    that many slices, so the slices H <= s < Nslice - H of the resampled series never hold zero fill"""
+    return int(np.ceil(0.5 * N * np.sin(np.deg2rad(abs(float(search_deg)))) - 1e-12))
+
+
+def axis_score(profile, H):
+    """Common-line score of a profile c[a][s] (``sino_axis_profile``): sum_s Var_a(c_a[s]) / sum_s mean_a(c_a[s])^2 over the slices
+    H <= s < Nslice - H (population variance over the projections).  Zero for a parallel-beam series whose axis runs along s."""
+    c = np.asarray(profile, np.float64)
+    if c.shape[1] - 2 * H <= 0:
+        raise ValueError(f"no slice is left between the borders of {H} slices: lower search_deg")
+    c = c[:, H:c.shape[1] - H]
+    return float(np.sum(np.var(c, axis=0)) / np.sum(np.mean(c, axis=0) ** 2))
+
+
+def axis_grid(search_deg, step_deg):
+    """the candidate rotations k * step_deg, |k| <= search_deg / step_deg, symmetric about 0"""
+    if not (search_deg > 0 and step_deg > 0):
+        raise ValueError("search_deg and step_deg must be positive")
+    K = int(np.floor(float(search_deg) / float(step_deg) + 1e-9))
+    return float(step_deg) * np.arange(-K, K + 1, dtype=np.float64)
+
+
+def axis_minimum(grid, scores):
+    """The first minimum of ``scores`` over ``grid``, refined by a 3-point parabola clamped to +-1/2 step.  A minimum on the grid's
+    border keeps its grid value and is flagged.  -> (rotation, index of the grid point, at_border)"""
+    sc = np.asarray(scores, np.float64)
+    k = int(np.argmin(sc))
+    border = k in (0, len(sc) - 1)
+    off = 0.0 if border else _parabola(-sc[k - 1], -sc[k], -sc[k + 1])
+    step = float(grid[1] - grid[0]) if len(grid) > 1 else 0.0
+    return float(grid[k] + off * step), k, bool(border)
 
 
 def center_of_mass_shifts(moments, nray, nslice):

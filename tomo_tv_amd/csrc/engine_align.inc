@@ -1,4 +1,5 @@
-// engine_align.inc -- tilt-series alignment: per-angle moments, windowed cross-correlation, resampling by per-angle shifts.
+// engine_align.inc -- tilt-series alignment: per-angle moments, windowed cross-correlation, resampling by per-angle shifts or affine
+// maps, per-slice mass profiles.
 // Part of tomo_engine.hip (included inside its extern "C" block, after engine_api.inc); kernels: kernels_align.hip.h.
 //
 // One whole-volume engine only: a shift along the tilt axis moves samples across slab boundaries, so an engine bound to a
@@ -113,5 +114,43 @@ int tomo_sino_shift(tomo_engine *e, int src, int dst, const float *shifts_host, 
     else hipLaunchKernelGGL((k_sino_shift<false>), grid, block, 0, e->stream, (const float *)s, d, (const int4 *)e->stage, e->n, e->nx, e->sx);
     LAUNCHCHK();
     HIPCHK(hipStreamSynchronize(e->stream));        // the table is read from this call's host memory
+    return TOMO_OK;
+}
+
+int tomo_sino_affine(tomo_engine *e, int src, int dst, const double *m_host)
+{
+    NEED_ALIGN(e);
+    if (!m_host) return fail(TOMO_ERR_ARG, "null matrices");
+    if (src == dst) return fail(TOMO_ERR_ARG, "source and destination must be different sinogram slots");
+    for (int i = 0; i < 6 * e->np; ++i) if (!std::isfinite(m_host[i])) return fail(TOMO_ERR_ARG, "non-finite matrix entry");
+    { int rc_ = order_after_async(e); if (rc_) return rc_; }
+    float *s, *d; int rc;
+    if ((rc = sino_slot(e, src, &s)) || (rc = sino_slot(e, dst, &d))) return rc;
+    if ((rc = ensure_stage(e, (size_t)e->np * 6 * sizeof(double)))) return rc;
+    HIPCHK(hipMemcpyAsync(e->stage, m_host, (size_t)e->np * 6 * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    const int blocks = (int)std::min<int64_t>(((int64_t)e->n * e->sx + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_sino_affine, dim3(blocks, e->np), dim3(256), 0, e->stream, (const float *)s, d, (const double *)e->stage, e->n, e->nx, e->sx);
+    LAUNCHCHK();
+    HIPCHK(hipStreamSynchronize(e->stream));        // the table is read from the caller's host memory
+    return TOMO_OK;
+}
+
+int tomo_sino_axis_profile(tomo_engine *e, int sino, double *out_host)
+{
+    NEED_ALIGN(e);
+    if (!out_host) return fail(TOMO_ERR_ARG, "null output");
+    { int rc_ = order_after_async(e); if (rc_) return rc_; }
+    float *g; int rc;
+    if ((rc = sino_slot(e, sino, &g))) return rc;
+    const int nblk = (e->n + AL_PROWS - 1) / AL_PROWS, nchunk = (e->nx + 63) / 64;
+    if ((rc = al_ensure(e, (void **)&e->al_part, &e->al_part_bytes, (size_t)e->np * nblk * e->nx * sizeof(double)))) return rc;
+    if ((rc = al_ensure(e, (void **)&e->al_out, &e->al_out_bytes, (size_t)e->np * e->nx * sizeof(double)))) return rc;
+    hipLaunchKernelGGL(k_sino_axis_profile, dim3(nchunk, nblk, e->np), dim3(256), 0, e->stream, (const float *)g, e->al_part, e->n, e->nx, e->sx);
+    LAUNCHCHK();
+    hipLaunchKernelGGL(k_sino_axis_profile_finish, dim3((e->np * e->nx + 255) / 256), dim3(256), 0, e->stream, (const double *)e->al_part,
+                       e->al_out, e->np, nblk, e->nx);
+    LAUNCHCHK();
+    HIPCHK(hipMemcpyAsync(out_host, e->al_out, (size_t)e->np * e->nx * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
     return TOMO_OK;
 }

@@ -1,4 +1,5 @@
 // kernels_align.hip.h -- tilt-series alignment on the sinogram layout: per-angle moments, windowed cross-correlation, resampling
+// by shifts and by affine maps, per-slice mass profiles
 // Part of kernels.hip.h (include that, not this: the families share helpers and constants in the order kernels.hip.h lists them).
 //
 // Projection a of a sinogram is the image X_a[r][s], ray r in [0, N), slice s in [0, Nslice): device row a * N + r, slice fastest,
@@ -200,6 +201,89 @@ __global__ __launch_bounds__(256) void k_sino_shift(const float *__restrict__ sr
         }
         D[idx] = o;
     }
+}
+
+// ---- resampling by per-angle affine maps (in-plane rotation, magnification, shift in one interpolation) -------------------------
+// dst_a[r][s] = bilinear(src_a)(r', s') with r' = m00 r + m01 s + m02, s' = m10 r + m11 s + m12, mat[a] = {m00, m01, m02, m10, m11,
+// m12} in binary64.  The layout and the grid are k_sino_shift's: lane = slice, s fastest, one 4-byte write per element, coalesced;
+// the reads of a wave are the source row(s) its destination row maps to -- for the few degrees of a tilt-axis correction a wave's 64
+// slices touch a handful of neighbouring source rows, 256-byte runs that the L2 serves.  The coordinates are binary64, evaluated
+// per element as fma(m00, r, fma(m01, s, m02)) and split into floor and fraction in binary64; only the fraction is rounded to
+// binary32 (a fraction that rounds to 1 is the next whole pixel, as in al_split).  Four binary64 FMAs, two floors and two conversions
+// per element beside one read and one write: at half the binary32 rate still an order below the time the bytes take.  Weights and
+// the four-tap expression are k_sino_shift's, operation for operation: a zero fraction drops its tap, so an identity copies the
+// source bits, a pure translation gives tomo_sino_shift's bits (wrap = 0) and an Inf next to a copied sample stays out of the
+// sum.  A tap outside [0, n) x [0, nx) is 0; a coordinate outside (-1, n) x (-1, nx) has no tap inside -- it gives 0 without a
+// conversion to int (a NaN from Inf - Inf of huge finite entries lands here too).  Padding slices of dst are written as zero.
+__global__ __launch_bounds__(256) void k_sino_affine(const float *__restrict__ src, float *__restrict__ dst, const double *__restrict__ mat,
+                                                     int n, int nx, int sx)
+{
+    const int a = blockIdx.y;
+    const double *m = mat + 6 * (size_t)a;
+    const double m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5];
+    const float *S = src + (size_t)a * n * sx;
+    float *D = dst + (size_t)a * n * sx;
+    auto fetch = [&](int i, int j) -> float {
+        if (i < 0 || i >= n || j < 0 || j >= nx) return 0.f;
+        return S[(size_t)i * sx + j];
+    };
+    const int total = n * sx;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+        const int r = idx / sx, s = idx - r * sx;
+        float o = 0.f;
+        if (s < nx) {
+            const double rp = fma(m00, (double)r, fma(m01, (double)s, m02));
+            const double sp = fma(m10, (double)r, fma(m11, (double)s, m12));
+            if (rp > -1.0 && rp < (double)n && sp > -1.0 && sp < (double)nx) {
+                const double fr = floor(rp), fs = floor(sp);
+                float tr = (float)(rp - fr), ts = (float)(sp - fs);
+                int i = (int)fr, j = (int)fs;
+                if (tr >= 1.f) { tr = 0.f; ++i; }
+                if (ts >= 1.f) { ts = 0.f; ++j; }
+                if (tr == 0.f && ts == 0.f) o = fetch(i, j);
+                else if (tr == 0.f) o = (1.f - ts) * fetch(i, j) + ts * fetch(i, j + 1);
+                else if (ts == 0.f) o = (1.f - tr) * fetch(i, j) + tr * fetch(i + 1, j);
+                else {
+                    const float wr = 1.f - tr, ws = 1.f - ts;
+                    o = (wr * ws) * fetch(i, j) + (wr * ts) * fetch(i, j + 1) + (tr * ws) * fetch(i + 1, j) + (tr * ts) * fetch(i + 1, j + 1);
+                }
+            }
+        }
+        D[idx] = o;
+    }
+}
+
+// ---- per-slice mass profile: c_a[s] = sum_r X_a[r][s] (the common line of a parallel-beam series: the same for every tilt) --------
+// Workgroup (ch, blk, a) takes the 64 slices [64 ch, 64 ch + 64) of AL_PROWS rays of projection a.  Lane = slice: wave w adds rows
+// r0 + w, r0 + w + 4, ... in ascending order, in binary64 from the first sample (a row read of a wave is 256 consecutive bytes); the
+// four waves' sums are added in wave order, one value per (angle, workgroup, slice), and k_sino_axis_profile_finish adds the
+// workgroups' in ascending order.
+constexpr int AL_PROWS = 64;
+
+__global__ __launch_bounds__(256) void k_sino_axis_profile(const float *__restrict__ g, double *__restrict__ part, int n, int nx, int sx)
+{
+    __shared__ double red[4][64];
+    const int a = blockIdx.z, blk = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int s = blockIdx.x * 64 + lane;
+    const int r0 = blk * AL_PROWS, r1 = min(n, r0 + AL_PROWS);
+    const float *base = g + (size_t)a * n * sx;
+    double acc = 0.0;
+    if (s < nx)
+        for (int r = r0 + w; r < r1; r += 4) acc += (double)base[(size_t)r * sx + s];
+    red[w][lane] = acc;
+    __syncthreads();
+    if (w == 0 && s < nx) part[((size_t)a * gridDim.y + blk) * nx + s] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+}
+
+// out[a][s] = the workgroups' sums added in ascending order
+__global__ void k_sino_axis_profile_finish(const double *__restrict__ part, double *__restrict__ out, int np, int nblk, int nx)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= np * nx) return;
+    const int a = i / nx, s = i - a * nx;
+    double acc = 0.0;
+    for (int b = 0; b < nblk; ++b) acc += part[((size_t)a * nblk + b) * nx + s];
+    out[i] = acc;
 }
 
 }  // namespace tomo

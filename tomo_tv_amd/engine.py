@@ -424,7 +424,7 @@ class _GroupBackend:
     def _no_align(self, *a):
         raise NotImplementedError("alignment runs on one whole-volume engine: a shift along the tilt axis crosses the sub-slabs")
 
-    c_sino_moments = c_sino_xcorr = c_sino_shift = _no_align
+    c_sino_moments = c_sino_xcorr = c_sino_shift = c_sino_affine = c_sino_axis_profile = _no_align
 
     def c_set_tilt_series(self, ptr):
         self._rows("set_sinogram", SINO_B, ptr, self.nray * self.nproj * 4)
@@ -1099,6 +1099,25 @@ class _EngineBase:
         if sh.shape != (self.Nproj, 2):
             raise ValueError(f"shifts must have shape {(self.Nproj, 2)}, got {sh.shape}")
         self.be.c("sino_shift", int(src), int(dst), _ptr(sh), int(bool(wrap)))
+
+    def sino_affine(self, src, dst, matrices):
+        """dst_p[r][s] = src_p(r', s'), bilinear, zeros outside the image, with r' = m00 r + m01 s + m02, s' = m10 r + m11 s + m12 and
+        ``matrices`` = (Nproj, 6) float64 of (m00, m01, m02, m10, m11, m12): the map from a destination sample to its source position
+        (``align.affine_matrices`` builds it from shifts, rotation and magnification).  Coordinates in binary64; an identity copies
+        the source bits, a pure translation gives the bits of ``sino_shift(wrap=False)``.  ``src`` != ``dst``."""
+        self._align_one_engine()
+        m = np.ascontiguousarray(matrices, dtype=np.float64)
+        if m.shape != (self.Nproj, 6):
+            raise ValueError(f"matrices must have shape {(self.Nproj, 6)}, got {m.shape}")
+        self.be.c("sino_affine", int(src), int(dst), _ptr(m))
+
+    def sino_axis_profile(self, which=SINO_B):
+        """(Nproj, Nslice) float64: c_p[s] = sum_r X_p[r][s] of sinogram slot ``which``, the mass of slice s seen by projection p --
+        the same for every p when the tilt axis runs along s."""
+        self._align_one_engine()
+        out = np.empty((self.Nproj, self.Nslice_), np.float64)
+        self.be.c("sino_axis_profile", int(which), _ptr(out))
+        return out
 
     def synchronize(self):
         self.be.c("synchronize")

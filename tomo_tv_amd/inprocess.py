@@ -249,7 +249,7 @@ class InProcessMultiGPU:
     def _no_align(self, *args, **kw):
         raise NotImplementedError("alignment runs on one whole-volume engine, not on slabs spread over devices")
 
-    sino_moments = sino_xcorr = sino_shift = _align_one_engine = _no_align
+    sino_moments = sino_xcorr = sino_shift = sino_affine = sino_axis_profile = _align_one_engine = _no_align
 
     # the reference's own multi-GPU queries (multigpuengine.cpp:385-421)
     def get_gpu_ids(self):

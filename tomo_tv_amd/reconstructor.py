@@ -112,7 +112,7 @@ class TomoGPU:
     def set_tilt_series(self, tiltSeries):
         self.Nslice, self.Nray, self.Nangles = tiltSeries.shape
         self.recon = None
-        self._align_kept, self._align_shifts = False, None      # a new series: nothing kept, nothing applied
+        self._align_kept, self._align_shifts, self._align_rot = False, None, None      # a new series: nothing kept, nothing applied
         t = _device_tensor(tiltSeries)
         if t is None:
             self.tomo.set_tilt_series(pytvlib.pack_tilt_series(tiltSeries))
@@ -268,6 +268,7 @@ class TomoGPU:
     # ---- alignment of the tilt series (an extension: the reference centres by mass on the host, cpu/utils/logger.py:237-252) ----
     ALIGN_SLOT = SINO_USER0          # sinogram slot that keeps the series as it was given
     ALIGN_MODEL_SLOT = SINO_USER0 + 39   # the last user slot: the leave-one-out model projections (refine_alignment)
+    ALIGN_SCRATCH_SLOT = SINO_USER0 + 38  # the candidates of estimate_tilt_axis_rotation
 
     def _align_engine(self):
         t = self.tomo
@@ -286,14 +287,86 @@ class TomoGPU:
         """Total shifts (Nangles, 2) of (dr, ds) -- along the rays, along the tilt axis -- applied to the series as it was given."""
         return np.zeros((self.Nangles, 2)) if self._align_shifts is None else np.array(self._align_shifts, np.float64)
 
-    def set_alignment(self, shifts, wrap=False):
+    def _align_resample(self, t, shifts, wrap=False, dst=SINO_B, rotation_deg=None):
+        """The one place that resamples the series as given (``ALIGN_SLOT``) into ``dst``: by ``sino_shift`` while no rotation or
+        magnification is stored, else by ONE affine pass that combines the stored rotation and magnification (or the candidate
+        ``rotation_deg``) with the shifts -- rotation and shifts never compound their interpolation.  The shifts are rounded to
+        binary32 on both paths, so a stored rotation of 0 with magnification 1 gives the bits of the shift path."""
+        stored = getattr(self, "_align_rot", None)
+        if stored is None and rotation_deg is None:
+            t.sino_shift(self.ALIGN_SLOT, dst, shifts, wrap=wrap)
+            return
+        if wrap:
+            raise ValueError("wrap=True cannot be combined with a rotation or magnification: the affine pass has no wrap form")
+        rot, mag = stored if stored is not None else (0.0, 1.0)
+        sh = np.asarray(shifts, np.float32).astype(np.float64)
+        t.sino_affine(self.ALIGN_SLOT, dst, align.affine_matrices(sh, rot if rotation_deg is None else rotation_deg, mag, self.Nray, self.Nslice))
+
+    def set_alignment(self, shifts, wrap=False, *, rotation_deg=None, magnification=None):
         """Apply total shifts to the series as it was given (not on top of earlier ones): projection a moves by (dr, ds) =
-        ``shifts[a]`` in the sense of ``np.roll``, bilinear for fractions, zeros (or with ``wrap`` the other edge) moving in."""
+        ``shifts[a]`` in the sense of ``np.roll``, bilinear for fractions, zeros (or with ``wrap`` the other edge) moving in.
+
+        ``rotation_deg`` / ``magnification`` (a scalar or one value per projection): the content is first rotated by
+        ``+rotation_deg`` about the image centre ((Nray-1)/2, (Nslice-1)/2), counter-clockwise from the r axis towards the s axis,
+        and scaled by ``magnification`` (``align.affine_matrices``); the series as given is resampled ONCE by the combined map.  Both
+        are remembered (``get_alignment_rotation``) and kept by later calls that name neither, ``refine_alignment`` included, until
+        ``set_tilt_series``; a keyword left ``None`` keeps its stored value (0 and 1 if there is none).  ``wrap`` must be False once a
+        rotation or magnification is stored or given."""
         t = self._align_engine()
         shifts = np.array(shifts, np.float64).reshape(self.Nangles, 2)
-        t.sino_shift(self.ALIGN_SLOT, SINO_B, shifts, wrap=wrap)
+        stored = getattr(self, "_align_rot", None)
+        if rotation_deg is not None or magnification is not None or stored is not None:
+            if wrap:
+                raise ValueError("wrap=True cannot be combined with a rotation or magnification: the affine pass has no wrap form")
+            rot, mag = stored if stored is not None else (np.zeros(self.Nangles), np.ones(self.Nangles))
+            if rotation_deg is not None:
+                rot = np.array(np.broadcast_to(np.asarray(rotation_deg, np.float64), (self.Nangles,)))
+            if magnification is not None:
+                mag = np.array(np.broadcast_to(np.asarray(magnification, np.float64), (self.Nangles,)))
+            if not (np.all(np.isfinite(rot)) and np.all(np.isfinite(mag)) and np.all(mag > 0)):
+                raise ValueError("rotation_deg must be finite and magnification positive and finite")
+            self._align_rot = (rot, mag)
+        self._align_resample(t, shifts, wrap=wrap)
         self._align_shifts = shifts
         return self.get_alignment()
+
+    def get_alignment_rotation(self):
+        """``(rotation_deg, magnification)``, each (Nangles,) float64, applied to the series as it was given (zeros and ones if
+        none was set)."""
+        stored = getattr(self, "_align_rot", None)
+        if stored is None:
+            return np.zeros(self.Nangles), np.ones(self.Nangles)
+        return np.array(stored[0], np.float64), np.array(stored[1], np.float64)
+
+    def estimate_tilt_axis_rotation(self, search_deg=10.0, step_deg=0.5, apply=True):
+        """In-plane rotation that brings the tilt axis onto the slice index, by the common-line property: for a parallel-beam series
+        whose axis runs along s, the mass of slice s, c_a[s] = sum_r X_a[r][s], is the same in every projection a.  For every
+        candidate phi = k ``step_deg`` in [-``search_deg``, ``search_deg``] the series as given is resampled by the current shifts (and
+        stored magnification) and phi into sinogram slot ``ALIGN_SCRATCH_SLOT`` (``sino_affine``), its profile taken
+        (``sino_axis_profile``) and scored by sum_s Var_a(c_a[s]) / sum_s mean_a(c_a[s])^2 over the slices H <= s < Nslice - H,
+        H = ceil(Nray/2 sin(search_deg)), which zero fill never reaches (``ValueError`` if none is left).  The grid minimum is refined
+        by a 3-point parabola clamped to +-1/2 step; a minimum on the grid's border is not refined and sets
+        ``self.align_axis_at_border`` (widen the search).  Returns the rotation ``set_alignment(rotation_deg=...)`` should receive, one
+        value for the whole series, and with ``apply`` passes it on with the current shifts.  ``self.align_axis_scores`` keeps
+        ``(grid, scores)``.  No reconstruction is needed.
+
+        Assumes a background near zero at the image borders (content that a rotation moves across the border changes the masses)
+        and a series already centred: run it after ``align_center_of_mass``, before ``refine_alignment``."""
+        t = self._align_engine()
+        H = align.axis_score_border(self.Nray, search_deg)
+        if self.Nslice - 2 * H <= 0:
+            raise ValueError(f"no slice is left between the borders of {H} slices: lower search_deg")
+        grid = align.axis_grid(search_deg, step_deg)
+        shifts = self.get_alignment()
+        scores = np.zeros(len(grid))
+        for k, phi in enumerate(grid):
+            self._align_resample(t, shifts, dst=self.ALIGN_SCRATCH_SLOT, rotation_deg=float(phi))
+            scores[k] = align.axis_score(t.sino_axis_profile(self.ALIGN_SCRATCH_SLOT), H)
+        rot, _, self.align_axis_at_border = align.axis_minimum(grid, scores)
+        self.align_axis_scores = (grid, scores)
+        if apply:
+            self.set_alignment(shifts, rotation_deg=rot)
+        return rot
 
     def align_center_of_mass(self):
         """The reference's rule per projection (cpu/utils/logger.py:237-252): roll, with wrap-around, so that the integer-truncated
@@ -365,7 +438,7 @@ class TomoGPU:
             shifts = shifts - peaks
             m = shifts[:, 1].mean()
             shifts[:, 1] -= m if subpixel else np.round(m)
-            t.sino_shift(self.ALIGN_SLOT, SINO_B, shifts, wrap=False)
+            self._align_resample(t, shifts)
             self._align_shifts = shifts.copy()
             self.align_peaks.append(peaks)
             self.align_history.append(shifts.copy())
