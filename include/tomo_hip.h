@@ -212,6 +212,40 @@ int tomo_sino_xcorr(tomo_engine *e, int sino_a, int sino_b, int max_shift, int s
 int tomo_sino_shift(tomo_engine *e, int src, int dst, const float *shifts_host, int wrap);   /* logger.py:249-250 */
 int tomo_sino_affine(tomo_engine *e, int src, int dst, const double *m_host);                /* [Nproj][6] */
 int tomo_sino_axis_profile(tomo_engine *e, int sino, double *out_host);                      /* [Nproj][Nslice] */
+
+/* ---- binning and prolongation between two engines (coarse-to-fine drivers) --------------------------------------------------
+ * `fine` and `coarse` are two different whole-volume engines on one device whose grids differ by factor = f, 2 or 4:
+ *     fine Nray == f * coarse Nray,   coarse Nslice == ceil(fine Nslice / f),   and for tomo_sino_bin the same Nproj.
+ * Nray must be divisible by f because the rule on rays is exact: parallelRay puts the rays at linspace(-(N-1)/2, (N-1)/2, N), and the
+ * centre of the fine rays f r', ..., f r' + f - 1 is f times coarse ray r' of an N/f geometry.  Nslice need not be: the trailing coarse
+ * slice takes the k < f fine slices that exist.
+ * Scale.  A coarse voxel is the MEAN of the fine voxels it covers, and the coarse engine's matrix measures chord lengths in coarse
+ * pixels, each f fine pixels long.  A ray through the binned volume therefore collects 1/f of what the f fine rays it replaces collect
+ * on average: a coarse sample is the mean of its f * k fine samples divided by f, i.e. (sum of the f * k samples) * 1 / (f^2 k), for
+ * full bins (k = f: 1 / f^3) and for the trailing partial bin (k < f) alike.  With it A_coarse bin(x) == bin(A_fine x) to rounding at
+ * 0 and 90 degrees, where a ray runs along a pixel row, and up to the discretisation of the strip model elsewhere.
+ *   tomo_sino_bin:   dst_a[r'][s'] = c * sum_{i<f} sum_{j<k} src_a[f r' + i][f s' + j],  k = min(f, Nslice - f s'),  c = 1 / (f^2 k)
+ *       rounded to binary32; the sum in binary32 in ascending (i, j) order, then one multiply by c.
+ *   tomo_volume_bin: dst[y'][z'][s'] = c * sum over the f x f x k block in ascending (y, z, s) order, the same c: the mean.
+ *   tomo_volume_prolong: cell-centred trilinear interpolation with clamp-to-edge, coarse `vol` into fine `fine_vol`.  Per axis the
+ *       fine index i sits at u = (i + 0.5) / f - 0.5; the taps are floor(u) and floor(u) + 1, clamped to the coarse range, and
+ *       t = u - floor(u) (1/4 or 3/4 at f = 2, an odd eighth at f = 4).  Each lerp is fma(t, b - a, a), along s, then z, then y; where
+ *       the clamp makes a and b the same sample it is copied.  The trailing partial coarse slice is treated as an ordinary cell.
+ *       Nothing is rescaled: means carry the same units.
+ * Hence, bit for bit: a constant volume prolongs to the same constant; a clamped edge copies (an Inf there stays an Inf); a constant
+ * sinogram bins to const / f wherever k is a power of two and the partial sums j * const, j <= f k, are binary32 numbers (any constant
+ * with log2(f k) spare low mantissa bits: the sum is sequential, and 3 * const already rounds for a constant that uses all 24); the
+ * pitch padding of the destination is written as zero; no source sample at slice index >= Nslice enters a result; the same bits from
+ * run to run.  An Inf in a bin gives Inf, never NaN.
+ * Ordering: the kernel runs on the destination engine's stream, which first waits (by an event, on the device) for what the source
+ * engine's stream has enqueued; the source engine's stream then waits for the kernel.  No host wait, and nothing to synchronise before
+ * the next call on either engine.  The destination counts as written (as after tomo_set_volume / tomo_set_sinogram); the source is read.
+ * TOMO_ERR_ARG: a null engine, the same engine twice, factor not 2 or 4, a bad slot, different devices, sizes that break the rule
+ * above.  TOMO_ERR_STATE: an engine bound to a communicator or whose geometry was released.  A refused call has enqueued nothing and
+ * leaves both engines usable. */
+int tomo_sino_bin(tomo_engine *fine, int sino, tomo_engine *coarse, int coarse_sino, int factor);
+int tomo_volume_bin(tomo_engine *fine, int vol, tomo_engine *coarse, int coarse_vol, int factor);
+int tomo_volume_prolong(tomo_engine *coarse, int vol, tomo_engine *fine, int fine_vol, int factor);
 int tomo_read_scalars(tomo_engine *e, double *out, int count);          /* synchronises the stream */
 /* the same without a pipeline bubble: _snapshot enqueues the copy of all slots behind the kernels that produce them (and behind
  * an evaluation in flight on the second stream) and returns; _read waits for that copy only.  The ASD-POCS drivers enqueue the

@@ -122,6 +122,9 @@ SIGNATURES = {
     "tomo_sino_shift": [_p, _i, _i, _p, _i],
     "tomo_sino_affine": [_p, _i, _i, _p],
     "tomo_sino_axis_profile": [_p, _i, _p],
+    "tomo_sino_bin": [_p, _i, _p, _i, _i],
+    "tomo_volume_bin": [_p, _i, _p, _i, _i],
+    "tomo_volume_prolong": [_p, _i, _p, _i, _i],
     "tomo_fgp_begin_vol": [_p, _i],
     "tomo_tv_fgp_vol": [_p, _i, _i, _f],
     "tomo_bind_fgp_halo": [_p, _p, _p, _p, _p],

@@ -19,3 +19,4 @@
 #include "kernels_fgp.hip.h"      // FGP-TV
 #include "kernels_pdhg.hip.h"     // Chambolle-Pock: dual sinogram, fused dual / divergence / primal pass
 #include "kernels_align.hip.h"    // tilt-series alignment: moments, windowed cross-correlation, resampling
+#include "kernels_bin.hip.h"      // binning of sinograms and volumes by 2 or 4, trilinear prolongation

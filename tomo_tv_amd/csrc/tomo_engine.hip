@@ -513,6 +513,7 @@ extern "C" {
 #include "engine_tv.inc"
 #include "engine_pdhg.inc"
 #include "engine_align.inc"
+#include "engine_bin.inc"
 #include "engine_comm.inc"
 #include "engine_options.inc"
 

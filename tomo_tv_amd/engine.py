@@ -425,6 +425,7 @@ class _GroupBackend:
         raise NotImplementedError("alignment runs on one whole-volume engine: a shift along the tilt axis crosses the sub-slabs")
 
     c_sino_moments = c_sino_xcorr = c_sino_shift = c_sino_affine = c_sino_axis_profile = _no_align
+    c_sino_bin = c_volume_bin = c_volume_prolong = _no_align
 
     def c_set_tilt_series(self, ptr):
         self._rows("set_sinogram", SINO_B, ptr, self.nray * self.nproj * 4)
@@ -1118,6 +1119,45 @@ class _EngineBase:
         out = np.empty((self.Nproj, self.Nslice_), np.float64)
         self.be.c("sino_axis_profile", int(which), _ptr(out))
         return out
+
+    # ---- binning and prolongation between two engines (include/tomo_hip.h: tomo_sino_bin / tomo_volume_bin / tomo_volume_prolong) ----
+    def _bin_partner(self, other):
+        """Both engines are whole-volume engines of this process (the rule of the alignment calls); -> the partner's handle."""
+        self._align_one_engine()
+        if not isinstance(other, _EngineBase):
+            raise TypeError("the partner must be an engine of this package")
+        other._align_one_engine()
+        return other.be.h
+
+    def binned_engine(self, factor):
+        """A new whole-volume engine of the grid ``factor`` times coarser -- Nray / f rays, ceil(Nslice / f) slices -- with this engine's
+        angles on its device."""
+        self._align_one_engine()
+        f, ang = int(factor), self._ctor_kw.get("angles_rad")
+        if ang is None:
+            raise NotImplementedError("an engine built from a matrix has no angles to build the coarse geometry from")
+        if f not in (2, 4) or self.Ny % f != 0:
+            raise ValueError("factor must be 2 or 4 and divide Nray")
+        return tomoengine(-(-self.Nslice_ // f), self.Ny // f, ang, device=self.gpuID)
+
+    def bin_sinogram_to(self, coarse, factor, src=SINO_B, dst=SINO_B):
+        """Sinogram slot ``dst`` of ``coarse`` = slot ``src`` of this engine binned by ``factor`` (2 or 4) along rays and slices:
+        the mean of the f x k fine samples divided by f (the coarse matrix measures lengths in coarse pixels; k < f only in the trailing
+        partial bin).  ``coarse`` has Nray / f rays, ceil(Nslice / f) slices and the same projections.  Enqueued on ``coarse``'s stream,
+        ordered against this engine's by events: no host wait."""
+        other = self._bin_partner(coarse)
+        check(self.be.L.tomo_sino_bin(self.be.h, int(src), other, int(dst), int(factor)))
+
+    def bin_volume_to(self, coarse, factor, src=VOL_RECON, dst=VOL_RECON):
+        """Volume ``dst`` of ``coarse`` = the mean of the f x f x k blocks of volume ``src`` of this engine."""
+        other = self._bin_partner(coarse)
+        check(self.be.L.tomo_volume_bin(self.be.h, int(src), other, int(dst), int(factor)))
+
+    def prolong_volume_to(self, fine, factor, src=VOL_RECON, dst=VOL_RECON):
+        """Volume ``dst`` of ``fine`` = volume ``src`` of this (coarse) engine, interpolated trilinearly between cell centres with
+        clamp-to-edge; no rescaling."""
+        other = self._bin_partner(fine)
+        check(self.be.L.tomo_volume_prolong(self.be.h, int(src), other, int(dst), int(factor)))
 
     def synchronize(self):
         self.be.c("synchronize")

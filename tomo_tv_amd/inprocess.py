@@ -250,6 +250,7 @@ class InProcessMultiGPU:
         raise NotImplementedError("alignment runs on one whole-volume engine, not on slabs spread over devices")
 
     sino_moments = sino_xcorr = sino_shift = sino_affine = sino_axis_profile = _align_one_engine = _no_align
+    bin_sinogram_to = bin_volume_to = prolong_volume_to = _no_align      # (two whole-volume engines: engine.py)
 
     # the reference's own multi-GPU queries (multigpuengine.cpp:385-421)
     def get_gpu_ids(self):

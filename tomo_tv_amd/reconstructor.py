@@ -113,6 +113,7 @@ class TomoGPU:
         self.Nslice, self.Nray, self.Nangles = tiltSeries.shape
         self.recon = None
         self._align_kept, self._align_shifts, self._align_rot = False, None, None      # a new series: nothing kept, nothing applied
+        self._pyramid = {}                                                             # ... and no binned copy of the old one
         t = _device_tensor(tiltSeries)
         if t is None:
             self.tomo.set_tilt_series(pytvlib.pack_tilt_series(tiltSeries))
@@ -143,6 +144,75 @@ class TomoGPU:
     def cgls(self, Niter=100, show_convergence=True):
         pytvlib.initialize_algorithm(self.tomo, "CGLS")
         return self._run_iterative("CGLS", Niter, show_convergence)
+
+    # ---- binning and coarse-to-fine reconstruction (an extension: engine.py bin_sinogram_to / prolong_volume_to) ----------------
+    def _bin_engine(self):
+        t = self.tomo
+        if not hasattr(t, "_align_one_engine"):
+            raise NotImplementedError("binning runs on one whole-volume engine")
+        t._align_one_engine()
+        return t
+
+    def binned(self, factor):
+        """A new ``TomoGPU`` of shape (ceil(Nslice / f), Nray / f, Nangles), f = ``factor`` (2 or 4), with the same angles on the same
+        device, whose tilt series is this object's current series (sinogram slot B, alignment included) binned on the device: the
+        mean of f x k samples divided by f, so that a reconstruction of it is the f-fold binned volume in the same units.  No host
+        copy of the series is made.  ``ValueError`` when ``Nray % factor != 0`` (the rays of the two grids would not line up)."""
+        f = int(factor)
+        if f not in (2, 4):
+            raise ValueError("factor must be 2 or 4")
+        if self.Nray % f != 0:
+            raise ValueError(f"Nray = {self.Nray} is not divisible by the factor {f}")
+        t = self._bin_engine()
+        c = object.__new__(TomoGPU)
+        c.Nslice, c.Nray, c.Nangles = -(-self.Nslice // f), self.Nray // f, self.Nangles
+        c.tomo = t.binned_engine(f)
+        c.verbose, c.recon, c.cost = getattr(self, "verbose", False), None, None
+        c._align_kept, c._align_shifts, c._align_rot, c._pyramid = False, None, None, {}
+        t.bin_sinogram_to(c.tomo, f)
+        return c
+
+    def _coarse(self, factor):
+        """The binned object of ``factor``, kept on ``self`` from its first use (its tables cost about 1 / f^2 of this engine's) until
+        ``set_tilt_series``; its series is binned again from the current one on every call (alignment may have moved it)."""
+        f = int(factor)
+        kept = self.__dict__.setdefault("_pyramid", {})
+        if f in kept:
+            self._bin_engine().bin_sinogram_to(kept[f].tomo, f)
+        else:
+            kept[f] = self.binned(f)
+        return kept[f]
+
+    def coarse_to_fine(self, factors=(4, 2), Niter=(30, 20, 10), alg="SIRT"):
+        """Reconstruct from zero at the coarsest of ``factors``, interpolate the result into the next level's reconstruction
+        (``prolong_volume_to``), run that level's iterations from there, and so on down to full resolution: ``Niter`` has one entry
+        per factor and a last one for this object.  ``alg`` is "SIRT" or "SART".  Returns the per-level cost arrays (the data distance
+        after every iteration, each at its own level); this object's ``cost`` is the last of them."""
+        factors = [int(f) for f in factors]
+        Niter = [int(n) for n in Niter]
+        if alg not in ("SIRT", "SART"):
+            raise ValueError("alg must be 'SIRT' or 'SART'")
+        if len(Niter) != len(factors) + 1:
+            raise ValueError("Niter needs len(factors) + 1 entries: one per factor and one for full resolution")
+        steps = factors + [1]
+        if any(f not in (2, 4) for f in factors) or any(a // b not in (2, 4) or a % b for a, b in zip(steps, steps[1:])):
+            raise ValueError("factors must fall from level to level in steps of 2 or 4: (4, 2), (4,) or (2,)")
+        self._bin_engine()
+        costs, prev, prev_f = [], None, None
+        for f, n in zip(steps, Niter):
+            rec = self if f == 1 else self._coarse(f)
+            pytvlib.initialize_algorithm(rec.tomo, alg)
+            if prev is None:
+                rec.tomo.restart_recon()
+            else:
+                prev.tomo.prolong_volume_to(rec.tomo, prev_f // f)
+            rec.cost = np.zeros(n)
+            for i in range(n):
+                pytvlib.run(rec.tomo, alg)
+                rec.cost[i] = rec.tomo.data_distance()
+            costs.append(rec.cost)
+            prev, prev_f = rec, f
+        return costs
 
     @_on_rank_threads
     def wbp(self, filter="ram-lak"):
@@ -401,7 +471,34 @@ class TomoGPU:
         t.be.set_tilt_series_tensor(model, SINO_PUBLIC, self.ALIGN_MODEL_SLOT)
         return self.ALIGN_MODEL_SLOT
 
-    def refine_alignment(self, Nouter=5, max_shift=8, recon=None, subpixel=True, leave_one_out=False, loo_iters=20):
+    def _align_pass(self, t, f, shifts, max_shift, recon, subpixel, leave_one_out, loo_iters):
+        """One pass of projection matching at binning factor ``f`` (1: on this object itself): model, correlation, peaks times f, new
+        totals, the series as given resampled by them, bookkeeping.  -> the new total shifts."""
+        rec = self if f == 1 else self._coarse(f)
+        ct = t if f == 1 else rec.tomo
+        if leave_one_out:
+            model = rec._model_leave_one_out(loo_iters)
+        else:
+            recon(rec)
+            ct.forward_projection()
+            model = SINO_G
+        C = ct.sino_xcorr(model, SINO_B, int(max_shift))
+        peaks, border = align.find_peaks(C, subpixel)
+        int_peaks = peaks if not subpixel else align.find_peaks(C, False)[0]
+        if f != 1:
+            peaks, int_peaks = peaks * f, int_peaks * f
+        self.align_int_peaks.append(int_peaks)
+        shifts = shifts - peaks
+        m = shifts[:, 1].mean()
+        shifts[:, 1] -= m if subpixel else np.round(m)
+        self._align_resample(t, shifts)
+        self._align_shifts = shifts.copy()
+        self.align_peaks.append(peaks)
+        self.align_history.append(shifts.copy())
+        self.align_at_border.append(border)
+        return shifts
+
+    def refine_alignment(self, Nouter=5, max_shift=8, recon=None, subpixel=True, leave_one_out=False, loo_iters=20, pyramid=None):
         """Projection matching.  Every outer pass reconstructs (``recon(self)``; default 20 SIRT iterations), projects the result,
         correlates each model projection with the measured one over shifts in [-max_shift, max_shift]^2 (``sino_xcorr``), moves the
         total shift of every projection against the peak it found and resamples the series AS GIVEN by the new totals (zeros move
@@ -417,32 +514,27 @@ class TomoGPU:
         ``leave_one_out``: the model of projection a comes from a SIRT reconstruction (``loo_iters`` iterations, ``recon`` is not used)
         that never saw projection a.  With few projections the plain form stalls -- the reconstruction reproduces every measured
         projection where it lies, so its model correlates best at zero shift (at 9 projections of 32 x 32 slices no peak leaves
-        (0, 0)) -- and this form does not; it costs ``Nangles`` reconstructions per pass and needs torch."""
+        (0, 0)) -- and this form does not; it costs ``Nangles`` reconstructions per pass and needs torch.
+
+        ``pyramid``: binning factors, coarsest first, e.g. ``(4, 2, 1)``; ``Nouter`` passes run per level.  A pass at factor f bins the
+        current series into the kept coarse object (``binned``), reconstructs and projects THERE (``recon`` is called with the coarse
+        object; ``leave_one_out`` works per level), correlates there with the same ``max_shift`` -- which reaches f * max_shift
+        full-resolution pixels -- and multiplies the peaks by f.  Totals, history, peaks and the resampling of the series as given stay
+        in full-resolution pixels; the lists get one entry per pass over all levels.  Factor 1 is the plain pass; ``None`` (default)
+        is ``(1,)``."""
         t = self._align_engine()
         if leave_one_out and recon is not None:
             raise ValueError("leave_one_out reconstructs by itself (loo_iters SIRT iterations): recon is not used")
         if recon is None:
             recon = lambda rec: rec.sirt(20, show_convergence=False)  # noqa: E731
+        levels = (1,) if pyramid is None else tuple(int(f) for f in pyramid)
+        if not levels or any(f not in (1, 2, 4) for f in levels):
+            raise ValueError("pyramid holds binning factors 4, 2 or 1, coarsest first")
         shifts = self.get_alignment()
         self.align_history, self.align_at_border, self.align_peaks, self.align_int_peaks = [], [], [], []
-        for _ in range(int(Nouter)):
-            if leave_one_out:
-                model = self._model_leave_one_out(loo_iters)
-            else:
-                recon(self)
-                t.forward_projection()
-                model = SINO_G
-            C = t.sino_xcorr(model, SINO_B, int(max_shift))
-            peaks, border = align.find_peaks(C, subpixel)
-            self.align_int_peaks.append(peaks if not subpixel else align.find_peaks(C, False)[0])
-            shifts = shifts - peaks
-            m = shifts[:, 1].mean()
-            shifts[:, 1] -= m if subpixel else np.round(m)
-            self._align_resample(t, shifts)
-            self._align_shifts = shifts.copy()
-            self.align_peaks.append(peaks)
-            self.align_history.append(shifts.copy())
-            self.align_at_border.append(border)
+        for f in levels:
+            for _ in range(int(Nouter)):
+                shifts = self._align_pass(t, f, shifts, max_shift, recon, subpixel, leave_one_out, loo_iters)
         return self.get_alignment()
 
     def _tensor_engine(self):
