@@ -50,6 +50,8 @@ enum tomo_scalar { TOMO_S_DD = 0,      /* sum (A x - b)^2            data_distan
                    TOMO_S_GNORM_ALL = 8, /* sum g^2 over the sub-slab engines of a slab group (tomo_scalar_sum_from) */
                    TOMO_S_DIFF2 = 7,   /* a second step-norm slot: ASD-POCS keeps the SART step norm here until the
                                           iteration's scalars are read together (one all-reduce, one read-back) */
+                   TOMO_S_DART_FREE = 9,      /* free voxels of the last tomo_dart_classify (an exact integer) */
+                   TOMO_S_DART_BOUNDARY = 10, /* boundary voxels of the last tomo_dart_classify */
                    TOMO_S_COUNT = 16 };
 
 const char *tomo_last_error(void);
@@ -246,6 +248,53 @@ int tomo_sino_axis_profile(tomo_engine *e, int sino, double *out_host);         
 int tomo_sino_bin(tomo_engine *fine, int sino, tomo_engine *coarse, int coarse_sino, int factor);
 int tomo_volume_bin(tomo_engine *fine, int vol, tomo_engine *coarse, int coarse_vol, int factor);
 int tomo_volume_prolong(tomo_engine *coarse, int vol, tomo_engine *fine, int fine_vol, int factor);
+
+/* ---- DART: discrete tomography for objects made of a few known grey levels ----------------------------------------------------
+ * K. J. Batenburg, J. Sijbers, "DART: a practical reconstruction algorithm for discrete tomography", IEEE Trans. Image Process.
+ * 20(9), 2011, pp. 2542-2553.  The reference has no DART; these calls are its building blocks on the resident volume, and
+ * TomoGPU.dart (reconstructor.py) is the loop: segment -> fix the interior at its grey level -> SIRT on the free voxels -> smooth.
+ * A voxel v = (s, y, z) of a volume has slice s in [0, Nslice) and y, z in [0, N).  Neighbours are NOT periodic (unlike the TV
+ * calls): a neighbour outside the volume does not exist.  The engine owns one STATE byte per voxel, made by tomo_dart_classify and
+ * used by the other calls: bits 0-3 label, bit 6 boundary, bit 7 free.
+ *   tomo_dart_classify: label(v) = the number of thresholds t_i, i < nthr, with x(v) >= t_i, compared in binary32 (NaN: 0; +Inf:
+ *       nthr).  0 <= nthr <= 15, thresholds finite and strictly ascending.  boundary(v) = some existing neighbour w of v has
+ *       label(w) != label(v); connectivity 6 = the faces, 26 = faces, edges and corners.  free(v) = boundary(v) || h(v) <
+ *       free_threshold with h(v) = mix(mix(idx) ^ seed), idx = (s N + y) N + z in uint32 arithmetic and
+ *       mix(a): a ^= a >> 16; a *= 0x7feb352d; a ^= a >> 15; a *= 0x846ca68b; a ^= a >> 16  -- a counter-based draw: the same set for
+ *       the same seed on any machine; free_threshold = 0 gives no random voxels, p * 2^32 a fraction p of them.  The numbers of free
+ *       and of boundary voxels land in TOMO_S_DART_FREE / TOMO_S_DART_BOUNDARY as exact integers.  Reads `vol`; enqueued, no wait.
+ *   tomo_dart_restore:  x(v) = grey_host[label(v)] where v is not free; a free voxel keeps its bits.  nlevels = the state's nthr + 1.
+ *   tomo_dart_segment:  the same for EVERY voxel, free or not: the volume then holds only the grey levels (the final segmentation).
+ *   tomo_dart_arm:      niter x { one iteration of tomo_sirt_data(e, vol, sino_b, 1) (the ASTRA SIRT step of tomoengine::SIRT,
+ *       gpu/utils/tomoengine.cpp:189-205); tomo_dart_restore }: SIRT whose fixed voxels are put back to their grey level after EVERY
+ *       iteration, so the residual of the fixed part is absorbed by the free voxels alone.  The SIRT kernels are the ones of
+ *       tomo_sirt_data, untouched.  Enqueued without a host wait.
+ *   tomo_dart_smooth:   dst(v) = fma(beta, m - x, x) for a free voxel, x = src(v), m = (the sum of the existing 26 neighbours of v in
+ *       src) * (1 / count): the sum in binary32 from the first term in ascending (dy, dz, ds) order without the centre, free and fixed
+ *       neighbours alike, 1 / count rounded once to binary32; a fixed voxel copies the bits of src.  src != dst, 0 <= beta <= 1.
+ *   tomo_dart_class_stats: out_host[c] = {sum of x(v), number of v} over the voxels with label(v) = c, c <= nthr (the label rule of
+ *       tomo_dart_classify for the thresholds given here; no state is needed or changed), in binary64, added in a fixed order in two
+ *       stages.  A voxel that is not finite is COUNTED in its class but NOT summed (the mean of the finite ones stays usable).  Waits.
+ *   tomo_dart_get_state: the state bytes as [Nslice][Ny][Nz].  Waits.
+ * Hence, bit for bit: tomo_dart_arm with every voxel free (free_threshold = 2^32 - 1 leaves out only h = 2^32 - 1) gives the bits of
+ * tomo_sirt_data(e, vol, sino_b, niter); with no voxel free it leaves a restored volume as it is; beta = 0 copies src; an Inf
+ * beside a fixed voxel never makes it NaN; the same state, counts, sums and volumes from run to run.  The pitch padding of a volume
+ * is written as zero and of the state as 0, and no sample at slice index >= Nslice enters a result.
+ * Bookkeeping: a volume written by restore, segment, arm or smooth counts as written (as after tomo_set_volume: its version moves on
+ * and a claim "G = A * vol" is dropped); classify and class_stats only read.
+ * One whole-volume engine only (a slab would need its neighbours' label planes): TOMO_ERR_STATE for an engine bound to a
+ * communicator or whose geometry was released, and for restore, segment, arm, smooth or get_state before any classify.
+ * TOMO_ERR_ARG: a null pointer, a bad slot, src == dst, nthr outside 0..15, nlevels != the state's nthr + 1, thresholds that are not
+ * finite and strictly ascending, connectivity other than 6 or 26, beta not in [0, 1] (NaN included), niter < 0, or
+ * Nslice * N * N >= 2^32.  A refused call has enqueued nothing and leaves the engine usable. */
+int tomo_dart_classify(tomo_engine *e, int vol, const float *thr_host, int nthr, int connectivity,
+                       uint32_t seed, uint32_t free_threshold);
+int tomo_dart_restore(tomo_engine *e, int vol, const float *grey_host, int nlevels);
+int tomo_dart_segment(tomo_engine *e, int vol, const float *grey_host, int nlevels);
+int tomo_dart_arm(tomo_engine *e, int vol, int sino_b, int niter, const float *grey_host, int nlevels);
+int tomo_dart_smooth(tomo_engine *e, int src, int dst, float beta);
+int tomo_dart_class_stats(tomo_engine *e, int vol, const float *thr_host, int nthr, double *out_host); /* [nthr+1][2], waits */
+int tomo_dart_get_state(tomo_engine *e, uint8_t *out_host);  /* [Nslice][Ny][Nz], waits */
 int tomo_read_scalars(tomo_engine *e, double *out, int count);          /* synchronises the stream */
 /* the same without a pipeline bubble: _snapshot enqueues the copy of all slots behind the kernels that produce them (and behind
  * an evaluation in flight on the second stream) and returns; _read waits for that copy only.  The ASD-POCS drivers enqueue the

@@ -15,6 +15,8 @@ SINO_B, SINO_G, SINO_R, SINO_USER0 = 0, 1, 2, 3
 SINO_YK_MODEL = 1000     # read-only: A * yk as tomo_fista_project_yk formed it
 VOL_USER0 = 5
 S_DD, S_DIFF, S_TV, S_GNORM, S_RMSE, S_COST, S_L1, S_DIFF2, S_GNORM_ALL, S_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 16
+S_DART_FREE, S_DART_BOUNDARY = 9, 10
+DART_LABEL_MASK, DART_BOUNDARY, DART_FREE = 15, 64, 128   # bits of a DART state byte
 FIELD_FGP_D, FIELD_FGP_P1 = 100, 101
 F32, F64 = 0, 1                       # tomo_dtype of the device data calls
 SINO_PACKED, SINO_PUBLIC = 0, 1       # tomo_sino_layout: [s][angle][ray] (the host calls') / [s][ray][angle] (what TomoGPU is given)
@@ -25,6 +27,7 @@ FORM_BP = ("all", "tile", "list")
 FORM_SART = ("angle", "tile", "resident")
 
 _i, _i64, _f, _p = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
+_u32 = ctypes.c_uint32
 _pp = ctypes.POINTER(ctypes.c_void_p)
 
 # name -> argtypes; every function returns int status except tomo_last_error
@@ -125,6 +128,13 @@ SIGNATURES = {
     "tomo_sino_bin": [_p, _i, _p, _i, _i],
     "tomo_volume_bin": [_p, _i, _p, _i, _i],
     "tomo_volume_prolong": [_p, _i, _p, _i, _i],
+    "tomo_dart_classify": [_p, _i, _p, _i, _i, _u32, _u32],
+    "tomo_dart_restore": [_p, _i, _p, _i],
+    "tomo_dart_segment": [_p, _i, _p, _i],
+    "tomo_dart_arm": [_p, _i, _i, _i, _p, _i],
+    "tomo_dart_smooth": [_p, _i, _i, _f],
+    "tomo_dart_class_stats": [_p, _i, _p, _i, _p],
+    "tomo_dart_get_state": [_p, _p],
     "tomo_fgp_begin_vol": [_p, _i],
     "tomo_tv_fgp_vol": [_p, _i, _i, _f],
     "tomo_bind_fgp_halo": [_p, _p, _p, _p, _p],

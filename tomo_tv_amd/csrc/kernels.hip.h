@@ -20,3 +20,4 @@
 #include "kernels_pdhg.hip.h"     // Chambolle-Pock: dual sinogram, fused dual / divergence / primal pass
 #include "kernels_align.hip.h"    // tilt-series alignment: moments, windowed cross-correlation, resampling
 #include "kernels_bin.hip.h"      // binning of sinograms and volumes by 2 or 4, trilinear prolongation
+#include "kernels_dart.hip.h"     // DART: label / boundary / free-set stencil, masked restore and smoother, per-class sums

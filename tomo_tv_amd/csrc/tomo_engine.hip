@@ -288,6 +288,11 @@ struct tomo_engine {
     double *al_part = nullptr, *al_mom = nullptr, *al_out = nullptr;
     float *al_mean = nullptr;
     size_t al_part_bytes = 0, al_out_bytes = 0;
+    // DART (engine_dart.inc): one state byte per voxel, the number of thresholds it was made with (-1: no segmentation yet), and the
+    // class statistics' partial sums [DART_STATS_BLOCKS + 1][16][2] (the last row: the result)
+    uint8_t *dart_state = nullptr;
+    int dart_nthr = -1;
+    double *dart_part = nullptr;
     // scalars
     double *d_scal = nullptr, *d_scal_own = nullptr, *d_part = nullptr, *d_part_aux = nullptr, *d_part_tv = nullptr;
     double *h_snap = nullptr;          // pinned: tomo_scalars_snapshot
@@ -514,6 +519,7 @@ extern "C" {
 #include "engine_pdhg.inc"
 #include "engine_align.inc"
 #include "engine_bin.inc"
+#include "engine_dart.inc"
 #include "engine_comm.inc"
 #include "engine_options.inc"
 

@@ -15,7 +15,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (F32, F64, FIELD_FGP_D, FIELD_FGP_P1, S_COST, S_COUNT, S_DD, S_DIFF, S_DIFF2, S_GNORM, S_GNORM_ALL, S_L1, S_RMSE, S_TV, SINO_B,
+from ._lib import (F32, F64, FIELD_FGP_D, FIELD_FGP_P1, S_COST, S_COUNT, S_DART_BOUNDARY, S_DART_FREE, S_DD, S_DIFF, S_DIFF2, S_GNORM, S_GNORM_ALL, S_L1, S_RMSE, S_TV, SINO_B,
                    SINO_G, SINO_PACKED, SINO_PUBLIC, VOL_ORIGINAL, VOL_RECON, VOL_RECON_OLD, VOL_TEMP, VOL_YK, check)
 from .distributed import SlabComm, slab_partition
 
@@ -1158,6 +1158,58 @@ class _EngineBase:
         clamp-to-edge; no rescaling."""
         other = self._bin_partner(fine)
         check(self.be.L.tomo_volume_prolong(self.be.h, int(src), other, int(dst), int(factor)))
+
+    # ---- DART building blocks (include/tomo_hip.h: tomo_dart_*; the loop is TomoGPU.dart) -----------------------------------------
+    def _dart_one_engine(self):
+        """One whole-volume engine: the label stencil of a slab would need its neighbours' boundary planes."""
+        if self.comm is not None or self.sub_slabs > 1 or not isinstance(self.be, _SlabBackend):
+            raise NotImplementedError("DART runs on one whole-volume engine (not on slabs sharded over ranks, devices or sub_slabs)")
+
+    def dart_classify(self, thresholds, vol=VOL_RECON, connectivity=26, seed=0, free_fraction=0.0):
+        """Segment volume ``vol`` into the engine's state bytes: label = the number of ``thresholds`` (ascending, at most 15) a voxel
+        reaches, boundary = a 6- or 26-neighbour inside the volume carries another label, free = boundary or drawn with probability
+        ``free_fraction`` by a counter-based hash of the voxel index and ``seed``.  -> (n_free, n_boundary)."""
+        self._dart_one_engine()
+        thr = np.ascontiguousarray(np.atleast_1d(thresholds), dtype=np.float32).ravel()
+        free_threshold = min(int(free_fraction * 2 ** 32), 2 ** 32 - 1)
+        if free_threshold < 0:
+            raise ValueError("free_fraction must not be negative")
+        self.be.c("dart_classify", int(vol), _ptr(thr), int(thr.size), int(connectivity), int(seed) & 0xffffffff, free_threshold)
+        n_free, n_boundary = self._scalars((S_DART_FREE, S_DART_BOUNDARY))
+        return int(n_free), int(n_boundary)
+
+    def dart_restore(self, grey_levels, vol=VOL_RECON, everywhere=False):
+        """Voxels that are not free take the grey level of their label; free voxels keep their bits.  ``everywhere``: all voxels do
+        (``tomo_dart_segment``: the volume then holds only the grey levels)."""
+        self._dart_one_engine()
+        g = np.ascontiguousarray(np.atleast_1d(grey_levels), dtype=np.float32).ravel()
+        self.be.c("dart_segment" if everywhere else "dart_restore", int(vol), _ptr(g), int(g.size))
+
+    def dart_arm(self, niter, grey_levels, vol=VOL_RECON, sino=SINO_B):
+        """``niter`` SIRT iterations on ``vol`` against sinogram ``sino`` with the fixed voxels put back to their grey level after every one."""
+        self._dart_one_engine()
+        g = np.ascontiguousarray(np.atleast_1d(grey_levels), dtype=np.float32).ravel()
+        self.be.c("dart_arm", int(vol), int(sino), int(niter), _ptr(g), int(g.size))
+
+    def dart_smooth(self, src, dst, beta):
+        """dst = src with every free voxel moved by ``beta`` towards the mean of its (up to 26) neighbours; fixed voxels are copied."""
+        self._dart_one_engine()
+        self.be.c("dart_smooth", int(src), int(dst), float(beta))
+
+    def dart_class_stats(self, thresholds, vol=VOL_RECON):
+        """(K, 2) float64 for K = len(thresholds) + 1 classes: the sum of the finite voxels of every class and its voxel count."""
+        self._dart_one_engine()
+        thr = np.ascontiguousarray(np.atleast_1d(thresholds), dtype=np.float32).ravel()
+        out = np.zeros((thr.size + 1, 2), np.float64)
+        self.be.c("dart_class_stats", int(vol), _ptr(thr), int(thr.size), _ptr(out))
+        return out
+
+    def dart_state(self):
+        """(Nslice, Nray, Nray) uint8: bits 0-3 label, bit 6 (``DART_BOUNDARY``) boundary, bit 7 (``DART_FREE``) free."""
+        self._dart_one_engine()
+        out = np.empty((self.Nslice_, self.Ny, self.Ny), np.uint8)
+        self.be.c("dart_get_state", _ptr(out))
+        return out
 
     def synchronize(self):
         self.be.c("synchronize")

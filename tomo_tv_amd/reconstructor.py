@@ -8,7 +8,7 @@ to the semantics of their canonical loops:
 import numpy as np
 
 from . import _lib, align, pytvlib
-from ._lib import S_DD, S_DIFF2, SINO_B, SINO_G, SINO_PUBLIC, SINO_USER0, VOL_RECON, VOL_YK
+from ._lib import S_DD, S_DIFF2, SINO_B, SINO_G, SINO_PUBLIC, SINO_USER0, VOL_RECON, VOL_USER0, VOL_YK
 from .engine import is_tensor, multigpuengine, tomoengine
 
 
@@ -23,6 +23,12 @@ def _device_tensor(a):
         import torch
         a = torch.from_dlpack(a)
     return a if a.is_cuda else None
+
+
+def dart_thresholds(levels):
+    """The thresholds between K ascending grey levels: the midpoints of adjacent levels, formed in binary64, as float32 (K - 1,)."""
+    g = np.asarray(levels, dtype=np.float64).ravel()
+    return (0.5 * (g[:-1] + g[1:])).astype(np.float32)
 
 
 def device_count():
@@ -536,6 +542,105 @@ class TomoGPU:
             for _ in range(int(Nouter)):
                 shifts = self._align_pass(t, f, shifts, max_shift, recon, subpixel, leave_one_out, loo_iters)
         return self.get_alignment()
+
+    # ---- DART: discrete tomography (an extension; Batenburg & Sijbers 2011; engine.py dart_*) -------------------------------------
+    def _dart_engine(self):
+        t = self.tomo
+        if not hasattr(t, "_dart_one_engine"):
+            raise NotImplementedError("DART runs on one whole-volume engine, not on a volume sharded over devices")
+        t._dart_one_engine()
+        return t
+
+    def _recon_range(self):
+        """(min, max) of the current reconstruction: a torch reduction on the device where torch sees it, else on the host."""
+        t = self.tomo
+        try:
+            import torch
+            on_device = torch.cuda.is_available() and torch.cuda.device_count() > t.gpuID
+        except ImportError:
+            on_device = False
+        if on_device:
+            x = t.get_volume_tensor(VOL_RECON)
+            return float(x.min()), float(x.max())
+        x = t.get_volume(VOL_RECON)
+        return float(x.min()), float(x.max())
+
+    def estimate_grey_levels(self, K, iters=20):
+        """K grey levels of the current reconstruction by 1-D Lloyd (k-means) iterations: start at ``linspace(min, max, K)``; per
+        iteration the thresholds are the midpoints of adjacent levels and every level moves to the mean of its class
+        (``dart_class_stats``: sums and counts in binary64 on the device); an empty class keeps its level.  -> float64 array (K,)."""
+        t = self._dart_engine()
+        K = int(K)
+        if not 1 <= K <= 16:
+            raise ValueError("K must be 1..16")
+        lo, hi = self._recon_range()
+        levels = np.linspace(lo, hi, K)
+        for _ in range(int(iters)):
+            if K == 1 or not np.all(np.diff(levels.astype(np.float32)) > 0):
+                break                                                   # a constant volume: nothing to separate
+            st = t.dart_class_stats(dart_thresholds(levels))
+            new = np.where(st[:, 1] > 0, st[:, 0] / np.maximum(st[:, 1], 1.0), levels)
+            if np.array_equal(new, levels):
+                break
+            levels = new
+        return levels
+
+    def dart(self, grey_levels, Niter=20, arm_iters=10, init_iters=50, fix_probability=0.85, smoothing=0.1, connectivity=26, seed=0,
+             segment=True):
+        """DART (Batenburg & Sijbers, IEEE TIP 20(9), 2011) for an object made of K known grey levels.
+
+        ``grey_levels``: K ascending values, or an int K: the levels are then estimated from the current reconstruction
+        (``estimate_grey_levels``, after the initial SIRT run below).  The thresholds are the midpoints of adjacent levels.
+        If the reconstruction is all zero (the ``restart_recon`` state) ``init_iters`` SIRT iterations make the starting point.
+        Then, ``Niter`` times: segment the reconstruction (``dart_classify``: boundary voxels are free, and every other voxel with
+        probability 1 - ``fix_probability``, drawn from ``seed_k = (seed * 0x9E3779B1 + k) mod 2^32``); set the fixed voxels to
+        their grey level; run ``arm_iters`` SIRT iterations in which the fixed voxels are put back after every one (``dart_arm``);
+        move every free voxel by ``smoothing`` towards the mean of its 26 neighbours (skipped at 0; the smoother writes into
+        volume slot ``VOL_USER0`` and the result is copied back, so WHATEVER THE CALLER KEPT IN ``VOL_USER0`` IS OVERWRITTEN).  With ``segment`` the loop ends with one more segmentation without random voxels and ``dart_restore(everywhere=True)``,
+        which sets EVERY voxel, boundary included, to the grey level of its label: the volume then holds only the K values.
+        ``get_dart_labels()`` gives the labels of the last segmentation.
+
+        -> dict of arrays, one entry per iteration: ``data_distance`` (||A x - b|| after the iteration), ``n_free``, ``n_boundary``;
+        ``grey_levels`` holds the levels used.  ``self.cost`` is replaced by the ``data_distance`` array, as the other drivers do."""
+        t = self._dart_engine()
+        pytvlib.initialize_algorithm(t, "SIRT")
+        lo, hi = self._recon_range()
+        if lo == 0.0 and hi == 0.0:
+            t.SIRT(int(init_iters))
+        if isinstance(grey_levels, (bool, np.bool_)):
+            raise TypeError("grey_levels must be a sequence of grey levels or an int K, not a bool")
+        if isinstance(grey_levels, (int, np.integer)):
+            levels = self.estimate_grey_levels(int(grey_levels))
+        else:
+            levels = np.asarray(grey_levels, dtype=np.float64).ravel()
+        grey = levels.astype(np.float32)
+        if grey.size < 1 or grey.size > 16 or not np.all(np.isfinite(grey)) or not np.all(np.diff(grey) > 0):
+            raise ValueError("grey_levels must be 1..16 finite, strictly ascending values (as float32)")
+        thr = dart_thresholds(levels)
+        free_fraction = 1.0 - float(fix_probability)
+        if not 0.0 <= free_fraction <= 1.0:
+            raise ValueError("fix_probability must lie in [0, 1]")
+        Niter = int(Niter)
+        out = {"data_distance": np.zeros(Niter), "n_free": np.zeros(Niter, np.int64), "n_boundary": np.zeros(Niter, np.int64),
+               "grey_levels": levels.copy()}
+        for k in range(Niter):
+            seed_k = (int(seed) * 0x9E3779B1 + k) & 0xffffffff
+            out["n_free"][k], out["n_boundary"][k] = t.dart_classify(thr, VOL_RECON, connectivity, seed_k, free_fraction)
+            t.dart_restore(grey)
+            t.dart_arm(int(arm_iters), grey)
+            if smoothing != 0:
+                t.dart_smooth(VOL_RECON, VOL_USER0, float(smoothing))
+                t.be.c("copy_volume", VOL_RECON, VOL_USER0)
+            out["data_distance"][k] = t.data_distance()
+        if segment:
+            t.dart_classify(thr, VOL_RECON, connectivity, 0, 0.0)
+            t.dart_restore(grey, everywhere=True)
+        self.cost = out["data_distance"]
+        return out
+
+    def get_dart_labels(self):
+        """(Nslice, Nray, Nray) uint8: the label (index into the grey levels) of every voxel in the last segmentation."""
+        return self._dart_engine().dart_state() & _lib.DART_LABEL_MASK
 
     def _tensor_engine(self):
         if not hasattr(self.tomo, "get_volume_tensor") or getattr(self.tomo, "comm", None) is not None:
