@@ -249,6 +249,32 @@ int tomo_sino_bin(tomo_engine *fine, int sino, tomo_engine *coarse, int coarse_s
 int tomo_volume_bin(tomo_engine *fine, int vol, tomo_engine *coarse, int coarse_vol, int factor);
 int tomo_volume_prolong(tomo_engine *coarse, int vol, tomo_engine *fine, int fine_vol, int factor);
 
+/* ---- dual-axis tomography: one volume shared by two engines with perpendicular tilt axes ------------------------------------
+ * A second tilt series about the perpendicular axis shrinks the missing wedge to a pyramid.  Every slice shares one system matrix and
+ * the lanes index slices, so the second axis needs no new projector: it needs a second ordinary engine whose "slices" run along the
+ * other axis, and the volume carried from one engine's layout into the other's.
+ * Geometry.  At zero tilt the rays of parallelRay (cpu/utils/pytvlib.py:8-121) run along the image's row index and ray j meets column
+ * j.  For the public volume X[s][y][z] the first tilt axis is s, the beam at zero tilt runs along y, and the perpendicular second axis
+ * is z.  Engine B therefore has slice index z, row index y (still the beam) and column index s:
+ *     X_B[z][y][s] = X_A[s][y][z],    b_B[z] = A_B vec(X[:, :, z]^T)  (the image with rows y and columns s).
+ * Both engines must hold a cube, Nslice == Nray == N, of the same N; Nproj may differ.  At zero tilt the two series' projections are
+ * transposes of each other, P_B[z][ray = s] = P_A[s][ray = z].  Mirrors and quarter turns of measured data are the caller's job.
+ *   tomo_volume_cross:      dst[z][y][s] = src[s][y][z].  A copy of bits: NaN payloads, +-Inf, -0.0 and denormals survive.  dst is not read.
+ *   tomo_volume_cross_axpy: dst[z][y][s] = fmaf(a, src[s][y][z], dst[z][y][s]), one rounding, then fmaxf(., 0) when clamp != 0.
+ *       IEEE arithmetic throughout: a = 0 leaves a finite-source element's dst bits (except that -0.0 + 0.0 = +0.0), a = 0 against
+ *       an Inf source gives NaN (0 * Inf), Inf stays Inf for a != 0.  fmaxf returns its other operand for a NaN, so with clamp a NaN
+ *       result is stored as 0 -- the rule of every clamp of this engine (tomo_positivity).
+ * Both write the pitch padding of the destination as zero, read no source element at slice index >= N, and give the same bits from
+ * run to run.  Ordering and bookkeeping are those of tomo_volume_bin above: the kernel runs on the destination engine's stream, which
+ * first waits (by an event, on the device) for what the source engine's stream has enqueued; the source's stream then waits for the
+ * kernel.  No host wait.  The destination counts as written (its claim "G = A * vol" is dropped); the source is read.
+ * TOMO_ERR_ARG: a null engine, the same engine twice, a bad slot, different devices, an engine that is not a cube, different N.
+ * TOMO_ERR_STATE: an engine bound to a communicator, one that is a slab of a larger volume (tomo_set_slab_edges), or one whose geometry
+ * was released -- crossing a sharded volume is an all-to-all between the ranks and is not provided.  A refused call has enqueued nothing
+ * and leaves both engines usable. */
+int tomo_volume_cross(tomo_engine *src, int src_vol, tomo_engine *dst, int dst_vol);
+int tomo_volume_cross_axpy(tomo_engine *src, int src_vol, tomo_engine *dst, int dst_vol, float a, int clamp);
+
 /* ---- DART: discrete tomography for objects made of a few known grey levels ----------------------------------------------------
  * K. J. Batenburg, J. Sijbers, "DART: a practical reconstruction algorithm for discrete tomography", IEEE Trans. Image Process.
  * 20(9), 2011, pp. 2542-2553.  The reference has no DART; these calls are its building blocks on the resident volume, and

@@ -128,6 +128,8 @@ SIGNATURES = {
     "tomo_sino_bin": [_p, _i, _p, _i, _i],
     "tomo_volume_bin": [_p, _i, _p, _i, _i],
     "tomo_volume_prolong": [_p, _i, _p, _i, _i],
+    "tomo_volume_cross": [_p, _i, _p, _i],
+    "tomo_volume_cross_axpy": [_p, _i, _p, _i, _f, _i],
     "tomo_dart_classify": [_p, _i, _p, _i, _i, _u32, _u32],
     "tomo_dart_restore": [_p, _i, _p, _i],
     "tomo_dart_segment": [_p, _i, _p, _i],

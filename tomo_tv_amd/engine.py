@@ -425,7 +425,7 @@ class _GroupBackend:
         raise NotImplementedError("alignment runs on one whole-volume engine: a shift along the tilt axis crosses the sub-slabs")
 
     c_sino_moments = c_sino_xcorr = c_sino_shift = c_sino_affine = c_sino_axis_profile = _no_align
-    c_sino_bin = c_volume_bin = c_volume_prolong = _no_align
+    c_sino_bin = c_volume_bin = c_volume_prolong = c_volume_cross = c_volume_cross_axpy = _no_align
 
     def c_set_tilt_series(self, ptr):
         self._rows("set_sinogram", SINO_B, ptr, self.nray * self.nproj * 4)
@@ -1158,6 +1158,21 @@ class _EngineBase:
         clamp-to-edge; no rescaling."""
         other = self._bin_partner(fine)
         check(self.be.L.tomo_volume_prolong(self.be.h, int(src), other, int(dst), int(factor)))
+
+    # ---- dual-axis: this engine's volume in the layout of an engine with the perpendicular tilt axis (include/tomo_hip.h:
+    # tomo_volume_cross / tomo_volume_cross_axpy; the drivers are dual_axis.DualAxisTomo) ------------------------------------------
+    def cross_volume_to(self, other, src=VOL_RECON, dst=VOL_RECON):
+        """Volume ``dst`` of ``other`` = volume ``src`` of this engine with the slice and the column index exchanged,
+        ``other[z][y][s] = self[s][y][z]``: the same object seen by an engine whose tilt axis is this engine's z.  A copy of bits.
+        Both engines hold a cube of the same N.  Enqueued on ``other``'s stream, ordered against this engine's by events: no host wait."""
+        partner = self._bin_partner(other)
+        check(self.be.L.tomo_volume_cross(self.be.h, int(src), partner, int(dst)))
+
+    def cross_axpy_volume_to(self, other, a, clamp=False, src=VOL_RECON, dst=VOL_RECON):
+        """``other[z][y][s] = fma(a, self[s][y][z], other[z][y][s])``, one rounding, then ``max(0, .)`` with ``clamp`` (a NaN is
+        clamped to 0).  IEEE arithmetic: ``a = 0`` against an Inf gives NaN."""
+        partner = self._bin_partner(other)
+        check(self.be.L.tomo_volume_cross_axpy(self.be.h, int(src), partner, int(dst), float(a), int(bool(clamp))))
 
     # ---- DART building blocks (include/tomo_hip.h: tomo_dart_*; the loop is TomoGPU.dart) -----------------------------------------
     def _dart_one_engine(self):
