@@ -169,10 +169,16 @@ int tomo_soft_threshold(tomo_engine *e, int vol, float lambda);         /* matri
 int tomo_fista_momentum(tomo_engine *e, float beta);                    /* tomoengine.cpp:381-384 */
 /* A yk = (1 + beta) A recon - beta A recon_old by linearity, from the projections the driver's cost evaluation made anyway
  * (gpu/reconstructor.py:121-155): call after tomo_data_distance_sq(RECON); a no-op unless provably valid; *done = 1 when the model
- * sinogram now holds A yk and the next tomo_sirt(YK) will start from it */
+ * sinogram now holds A yk and the next tomo_sirt(YK) will start from it.  That projection is dropped by any write to YK and by any
+ * write-intent access of RECON (the caller has left the iteration it was formed in): the next tomo_sirt(YK) then projects again */
 int tomo_fista_project_yk(tomo_engine *e, int *done);
 
-/* ---- scalar reductions: partial sums of this slab land in the device scalar buffer ------------------ */
+/* ---- scalar reductions: partial sums of this slab land in the device scalar buffer ------------------
+ * The sums are binary64 and gathered through 256 partial-sum slots by atomic additions, so a value is reproducible to the rounding of
+ * the order of those additions (the tests compare such values at 1e-12 relative: a figure chosen far above the 2^-53 of one
+ * rounding, not a measured one).  The projector's sums (TOMO_S_DD, TOMO_S_COST) and the tracked back-projection's give every WAVE a slot
+ * of its own: in a launch of at most 256 waves no two additions meet in one slot, so by construction the value does not depend on
+ * the order in which the waves finish (larger launches share slots and vary in the last bits as before). */
 int tomo_data_distance_sq(tomo_engine *e, int vol);                     /* tomoengine.cpp:410-413 -> TOMO_S_DD (also fills G) */
 /* the same evaluation on a second stream, for a volume the main sequence no longer writes (e.g. the TEMP copy);
  * tomo_async_wait (also implied by tomo_read_scalars) orders the main stream behind it */
@@ -328,6 +334,17 @@ int tomo_read_scalars(tomo_engine *e, double *out, int count);          /* synch
  * examples/sim_ASD.py:90-94). */
 int tomo_scalars_snapshot(tomo_engine *e);
 int tomo_scalars_snapshot_read(tomo_engine *e, double *out, int count);
+/* Pending work and the other reduction users.  Three things can be in flight between two calls: a tomo_scalars_snapshot not yet read,
+ * a tomo_data_distance_sq_async not yet waited for, and the scalars of a tomo_tv_gd_tracked whose read-back the host has deferred
+ * (a snapshot).  tomo_dart_classify, tomo_dart_class_stats, tomo_sino_moments, tomo_sino_xcorr and tomo_sino_axis_profile may be called
+ * while any of them is: none refuses, none cancels the pending item or changes what it delivers, and both sides deliver what the
+ * un-interleaved order delivers, bit for bit.  They run on the engine's stream behind everything enqueued so far; a snapshot is a copy that was
+ * enqueued BEFORE them, so it keeps the slot values of that moment (TOMO_S_DART_* of a later classify are not in it); the evaluation
+ * on the second stream owns its own partial sums and only TOMO_S_DD, which none of the five writes, and the alignment calls (which
+ * may read TOMO_SINO_G) first order the engine's stream behind it.  The five C calls leave the evaluation pending.  tomo_read_scalars, however,
+ * implies tomo_async_wait, as stated above: a host that fetches TOMO_S_DART_* with it after tomo_dart_classify (the Python wrapper
+ * does) has thereby COMPLETED the evaluation -- its TOMO_S_DD is the same value -- and a later tomo_async_wait is a no-op.  Only ONE snapshot can
+ * be pending: a second tomo_scalars_snapshot replaces the first. */
 int tomo_bind_scalar_buffer(tomo_engine *e, void *device_doubles);      /* >= TOMO_S_COUNT doubles, e.g. a torch tensor */
 
 /* ---- 3-D total variation ---------------------------------------------------------------------------- */
@@ -562,6 +579,10 @@ int tomo_set_option(tomo_engine *e, const char *name, int value);
  * "table_kib" (device memory of the tables built at creation: every kernel family's, eagerly), "create_ms" (what creation took),
  * "stage_bytes" (bytes of the staging buffer the HOST data calls copy through, clamped to 2^31 - 1; 0 = never allocated: the device
  * data calls, tomo_set_volume_device ..., neither allocate nor use it),
+ * "pool_bytes" (the sizes of every live device allocation of the engine's registry, summed and clamped to 2^31 - 1: two engines of one
+ * geometry that made the same calls with the same sizes hold the same number, in whatever order the sizes came -- a scratch buffer
+ * that is regrown is released first, none is held twice; an engine that holds 2 GiB or more reads as 2^31 - 1, where an equality of
+ * two engines says nothing),
  * "form_fp" / "form_bp" / "form_sart": which kernel family the all-angle forward projection, the all-angle back projection and the
  * SART sweep of THIS engine run as under the options in force (tomo_form; one function of the engine decides it for the launchers
  * and for this query: tomo_engine.hip select_forms) */

@@ -111,6 +111,38 @@ int main(int argc, char **)
         dst.pool.release_all();
         REQUIRE(!live(moved) && dst.vol == nullptr && nlive() == 0 && g_bad_free == 0, "the destination's frees it, through the new slot");
     }
+    {   // a scratch buffer that grows on demand (ensure_stage, al_ensure: keep while large enough, else release and allocate anew), used by
+        // callers of different sizes in a row: every byte a caller asked for is writable (ASan), the old block is freed once, and
+        // bytes() ends at the largest request whatever the order -- what "pool_bytes" compares between a used and a fresh engine
+        struct Scratch { void *p = nullptr; size_t have = 0; };
+        auto ensure = [](DevPool &pool, Scratch &s, size_t bytes) {
+            if (s.have >= bytes) return 0;
+            if (s.p) { if (pool.release(s.p)) return 1; s.have = 0; }
+            if (int rc = pool.alloc(DevPool::ENGINE, &s.p, bytes)) return rc;
+            s.have = bytes;
+            return 0;
+        };
+        const size_t order_a[] = {4096, 432, 6144, 1152, 144, 4096, 72}, order_b[] = {6144, 4096, 4096, 1152, 432, 144, 72};
+        size_t total[2] = {0, 0};
+        int k = 0;
+        for (const size_t *order : {order_a, order_b}) {
+            DevPool pool(host_alloc, host_free);
+            Scratch s;
+            void *other = nullptr;
+            REQUIRE(pool.alloc(DevPool::ENGINE, &other, 1000) == 0, "alloc");
+            int grown = 0;
+            for (int i = 0; i < 7; ++i) {
+                void *const before = s.p;
+                REQUIRE(ensure(pool, s, order[i]) == 0 && s.have >= order[i], "ensure(%zu)", order[i]);
+                if (s.p != before) { ++grown; REQUIRE(!before || !live(before), "the outgrown block was freed"); }
+                for (size_t b = 0; b < order[i]; ++b) static_cast<char *>(s.p)[b] = (char)i;      // the whole request is the caller's to write
+                REQUIRE(pool.bytes() == 1000 + s.have && nlive() == 2, "one scratch block at a time: %zu bytes, %zu blocks", pool.bytes(), nlive());
+            }
+            REQUIRE(grown == (k == 0 ? 2 : 1) && s.have == 6144, "grown %d times to %zu", grown, s.have);
+            total[k++] = pool.bytes();
+        }
+        REQUIRE(total[0] == total[1] && nlive() == 0 && g_bad_free == 0, "the same bytes in either order: %zu / %zu", total[0], total[1]);
+    }
     {   // first-use allocations from the main thread and a chain helper thread at once: no entry lost
         DevPool pool(host_alloc, host_free);
         constexpr int N = 2000;

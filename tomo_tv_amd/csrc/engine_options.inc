@@ -28,6 +28,7 @@ int tomo_get_option(tomo_engine *e, const char *name, int *value)
     if (std::strcmp(name, "table_kib") == 0) { *value = (int)std::min<size_t>(e->table_bytes >> 10, 0x7FFFFFFF); return TOMO_OK; }   // device tables built at creation
     if (std::strcmp(name, "create_ms") == 0) { *value = (int)std::min(e->create_ms + 0.5, 2147483647.0); return TOMO_OK; }           // what creating this engine took
     if (std::strcmp(name, "stage_bytes") == 0) { *value = (int)std::min<size_t>(e->stage_bytes, 0x7FFFFFFF); return TOMO_OK; }   // staging buffer of the host data calls (0: never allocated)
+    if (std::strcmp(name, "pool_bytes") == 0) { *value = (int)std::min<size_t>(e->pool.bytes(), 0x7FFFFFFF); return TOMO_OK; }   // the registry's live allocations, summed
     if (std::strcmp(name, "tv_halo_fold") == 0) { *value = e->tv_halo_fold; return TOMO_OK; }
     if (std::strcmp(name, "form_fp") == 0) { *value = select_forms(e).fp; return TOMO_OK; }
     if (std::strcmp(name, "form_bp") == 0) { *value = select_forms(e).bp; return TOMO_OK; }

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void k_bp_angle(float *__restrict__ x, const C
     }
     if (TRACK) {
         local = wave_sum(local);
-        if (lane == 0) atomicAdd(&part[blockIdx.x & (NPART - 1)], local);
+        if (lane == 0) atomicAdd(&part[(blockIdx.x * 4 + wave) & (NPART - 1)], local);   // a slot per wave: no two waves of a grid of up to NPART waves add into one (the order of such adds is not fixed)
     }
 }
 

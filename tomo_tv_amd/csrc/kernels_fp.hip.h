@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256) void k_fp_rows_g(const float *__restrict__ x, 
     }
     if (MODE == FP_DD || MODE == FP_POISSON) {
         local = wave_sum(local);
-        if (lane == 0) atomicAdd(&part[blockIdx.x & (NPART - 1)], local);
+        if (lane == 0) atomicAdd(&part[(blockIdx.x * 4 + wave) & (NPART - 1)], local);   // a slot per wave: no two waves of a grid of up to NPART waves add into one (the order of such adds is not fixed)
     }
 }
 
@@ -517,7 +517,7 @@ __global__ __launch_bounds__(256) void k_fp_tile_reduce(const float *__restrict_
     }
     if (MODE == FP_DD || MODE == FP_POISSON) {
         local = wave_sum(local);
-        if (lane == 0) atomicAdd(&dpart[blockIdx.x & (NPART - 1)], local);
+        if (lane == 0) atomicAdd(&dpart[(blockIdx.x * 4 + wave) & (NPART - 1)], local);   // a slot per wave: no two waves of a grid of up to NPART waves add into one (the order of such adds is not fixed)
     }
 }
 

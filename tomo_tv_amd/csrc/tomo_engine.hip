@@ -390,6 +390,11 @@ static int get_vol(tomo_engine *e, int id, float **out)
 {
     if (id < 0 || id >= TOMO_VOL_SLOTS) return fail(TOMO_ERR_ARG, "bad volume id");
     ++e->vol_version[id];                               // the caller may write it
+    // A REPRODUCIBILITY choice, not a staleness fix: g_yk is still exactly A * YK after a write to RECON (neither YK nor g_yk was touched;
+    // a write to YK drops the claim through the version above).  But g_yk was formed by linearity and does not have the bits of a
+    // projection of YK, and a run in which the caller steps in between tomo_fista_project_yk and the next tomo_sirt on YK is required to
+    // give the bits of "fp_reuse" = 0 (tests/test_gpu_sequences.py, section (c)).  The FISTA driver never writes RECON there: no cost.
+    if (id == TOMO_VOL_RECON) e->yk_claim.valid = false;
     if (e->old_is_recon && (id == TOMO_VOL_RECON || id == TOMO_VOL_RECON_OLD)) {
         e->old_is_recon = false;
         float *src, *dst; int rc;
