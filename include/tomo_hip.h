@@ -281,6 +281,43 @@ int tomo_volume_prolong(tomo_engine *coarse, int vol, tomo_engine *fine, int fin
 int tomo_volume_cross(tomo_engine *src, int src_vol, tomo_engine *dst, int dst_vol);
 int tomo_volume_cross_axpy(tomo_engine *src, int src_vol, tomo_engine *dst, int dst_vol, float a, int clamp);
 
+/* ---- a volume resampled by a 3-D affine map (positioning a tomogram; the pose of the second series of a dual-axis set) ----------
+ * Two measured tilt series are never related by the exact transpose above: the grid is turned by hand, and the two tomograms differ
+ * by a small rigid motion in all three axes.  These two calls apply such a motion (they do not estimate it): the volume counterpart of
+ * tomo_sino_affine, rotation, magnification and shift in ONE trilinear interpolation.
+ * Both volumes are addressed in their engine's public index order X[s][y][z].  m_host = {m00, m01, m02, m03, m10, .., m13, m20, ..,
+ * m23}, a row-major 3 x 4 matrix in binary64, maps a DESTINATION voxel (s, y, z) to its SOURCE position (s', y', z') -- the
+ * convention of tomo_sino_affine:
+ *     s' = fma(m00, s, fma(m01, y, fma(m02, z, m03))),  y' = fma(m10, s, fma(m11, y, fma(m12, z, m13))),  z' = fma(m20, s, fma(m21, y, fma(m22, z, m23)))
+ *   tomo_volume_affine:      dst[s][y][z] = trilinear(src)(s', y', z').  Taps outside [0, Nslice_src) x [0, N_src) x [0, N_src) are 0;
+ *       there is no wrap form.  dst is not read.
+ *   tomo_volume_affine_axpy: dst[s][y][z] = fmaf(a, that value, dst[s][y][z]), one rounding, then fmaxf(., 0) when clamp != 0: the
+ *       rules of tomo_volume_cross_axpy, its NaN and Inf behaviour included (a = 0 against an Inf value gives NaN; with clamp a NaN
+ *       result is stored as 0).
+ * Arithmetic.  Each coordinate is evaluated in binary64 as the chain of three fused multiply-adds written above and split there
+ * into floor and fraction.  Only the fraction t is rounded to binary32; a fraction that rounds to 1 is the next whole voxel with
+ * t = 0.  Per axis the binary32 weights are w0 = 1 - t and w1 = t.  An axis whose fraction is zero keeps only its first tap, with
+ * w0 = 1 exactly: the dropped tap is neither loaded nor multiplied.  With x[dy][dz][ds] the tap at (floor s' + ds, floor y' + dy,
+ * floor z' + dz), the kept taps are combined in ascending (dy, dz, ds) order, ds fastest, every operation rounded once:
+ *     o = ((wy[0] * wz[0]) * ws[0]) * x[0][0][0];  then for every further kept tap  o = fmaf((wy[dy] * wz[dz]) * ws[ds], x[dy][dz][ds], o)
+ * and a voxel whose three fractions are all zero takes the bits of its single tap.  A coordinate outside (-1, size) has no tap inside
+ * and gives 0.  Hence, bit for bit: an identity matrix on equal sizes copies the source (NaN payloads, -0.0 and denormals survive);
+ * the permutation {0,0,1,0, 0,1,0,0, 1,0,0,0} between two cube engines gives the bits of tomo_volume_cross; a whole-voxel translation
+ * copies samples and stores zeros where it runs out; quarter turns and flips copy samples; an Inf next to a copied sample never
+ * becomes NaN.  One producer and one fixed expression per output word, no atomics: the same bits from run to run.
+ * Engines.  src and dst are whole-volume engines on one device; their sizes may differ and need not be cubes.  They may be two
+ * engines, or THE SAME engine with two different slots.  Both calls write the pitch padding of the destination as zero and read no
+ * source element at slice index >= Nslice.  Ordering and bookkeeping are those of tomo_volume_cross: the source is read, the
+ * destination counts as written (its claim "G = A * vol" is dropped); with two engines the kernel runs on the destination engine's
+ * stream, which first waits (by an event, on the device) for what the source engine's stream has enqueued, and the source's stream
+ * then waits for the kernel; with one engine the kernel runs on that engine's stream alone.  No host wait in either case: m_host is
+ * read before the call returns.
+ * TOMO_ERR_ARG: a null engine or pointer, a bad slot, the same engine with src_vol == dst_vol, different devices, a non-finite
+ * matrix entry.  TOMO_ERR_STATE: an engine bound to a communicator, one that is a slab of a larger volume (tomo_set_slab_edges), or
+ * one whose geometry was released.  A refused call has enqueued nothing and leaves both engines usable. */
+int tomo_volume_affine(tomo_engine *src, int src_vol, tomo_engine *dst, int dst_vol, const double *m_host /* [12] */);
+int tomo_volume_affine_axpy(tomo_engine *src, int src_vol, tomo_engine *dst, int dst_vol, const double *m_host, float a, int clamp);
+
 /* ---- DART: discrete tomography for objects made of a few known grey levels ----------------------------------------------------
  * K. J. Batenburg, J. Sijbers, "DART: a practical reconstruction algorithm for discrete tomography", IEEE Trans. Image Process.
  * 20(9), 2011, pp. 2542-2553.  The reference has no DART; these calls are its building blocks on the resident volume, and

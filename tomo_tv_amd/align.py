@@ -72,6 +72,60 @@ def affine_matrices(shifts, rotation_deg, magnification, N, Nslice):
     return M
 
 
+def rotation_3d(rotation_deg):
+    """The 3 x 3 content rotation of ``affine_matrix_3d`` in (s, y, z) coordinates, ``Rz @ Ry @ Rs`` for ``rotation_deg`` = (about s,
+    about y, about z); multiples of 90 degrees give exact 0 and +-1."""
+    a, b, g = (float(v) for v in rotation_deg)
+    (ca, sa), (cb, sb), (cg, sg) = _cos_sin_deg(a), _cos_sin_deg(b), _cos_sin_deg(g)
+    Rs = np.array([[1.0, 0.0, 0.0], [0.0, ca, -sa], [0.0, sa, ca]])
+    Ry = np.array([[cb, 0.0, sb], [0.0, 1.0, 0.0], [-sb, 0.0, cb]])
+    Rz = np.array([[cg, -sg, 0.0], [sg, cg, 0.0], [0.0, 0.0, 1.0]])
+    return Rz @ Ry @ Rs
+
+
+def affine_matrix_3d(rotation_deg=(0, 0, 0), shift=(0, 0, 0), magnification=1.0, src_shape=None, dst_shape=None, matrix=None):
+    """The 12 float64 entries (row-major 3 x 4) for ``tomoengine.volume_affine_to``: the map from a destination voxel (s, y, z) to its
+    source position.  The content of a volume of ``src_shape`` = (Nslice, N, N) is rotated about the volume centre (each axis at
+    (size - 1) / 2), scaled by ``magnification`` about it, then moved by ``+shift`` = (ds, dy, dz) voxels (``np.roll``'s sense) into a
+    volume of ``dst_shape`` (default: ``src_shape``), centre onto centre:  ``dst = c_dst + mag R (src - c_src) + shift``, and the
+    result is the inverse map  ``src = R^T / mag . (dst - c_dst - shift) + c_src``.
+
+    ``rotation_deg`` = (about s, about y, about z), applied in that order (R = Rz Ry Rs), each right-handed in the cyclic order
+    s -> y -> z -> s.  By what a point on the +y axis (as seen from the centre) does under a small positive angle: about s it moves
+    towards +z; about y it stays where it is (a point on the +z axis moves towards +s); about z it moves towards -s (a point on the
+    +s axis moves towards +y).  ``matrix=`` takes the 3 x 3 content rotation R directly, in (s, y, z) coordinates, instead of the angles.
+
+    Rotations by multiples of 90 degrees take cos and sin as exact 0 and +-1, so quarter turns between equal cubes are integer
+    matrices (samples onto samples); no rotation with magnification 1 gives the exact translation."""
+    if src_shape is None:
+        raise ValueError("src_shape = (Nslice, N, N) is required")
+    src = np.asarray(src_shape, np.float64).ravel()
+    dst = src if dst_shape is None else np.asarray(dst_shape, np.float64).ravel()
+    d = np.asarray(shift, np.float64).ravel()
+    mag = float(magnification)
+    if src.shape != (3,) or dst.shape != (3,) or d.shape != (3,) or np.any(src < 1) or np.any(dst < 1):
+        raise ValueError("src_shape, dst_shape and shift must have three entries, the shapes positive")
+    if not np.isfinite(mag) or mag <= 0.0:
+        raise ValueError("magnification must be positive and finite")
+    if matrix is None:
+        rot = np.asarray(rotation_deg, np.float64).ravel()
+        if rot.shape != (3,) or not np.all(np.isfinite(rot)):
+            raise ValueError("rotation_deg must be three finite angles (about s, about y, about z)")
+        R = rotation_3d(rot)
+    else:
+        R = np.asarray(matrix, np.float64)
+        if R.shape != (3, 3) or not np.all(np.isfinite(R)):
+            raise ValueError("matrix must be a finite 3 x 3 rotation")
+    if not np.all(np.isfinite(d)):
+        raise ValueError("shift must be finite")
+    A = R.T / mag if mag != 1.0 else R.T.copy()
+    cs, cd = 0.5 * (src - 1.0), 0.5 * (dst - 1.0)
+    M = np.empty((3, 4))
+    M[:, :3] = A
+    M[:, 3] = cs - A @ (cd + d)
+    return M.ravel()
+
+
 def axis_score_border(N, search_deg):
     """H = ceil(N/2 sin(search_deg)): a rotation by up to ``search_deg`` about the centre moves a sample of a row of N rays by at most
     that many slices, so the slices H <= s < Nslice - H of the resampled series never hold zero fill"""

@@ -21,4 +21,5 @@
 #include "kernels_align.hip.h"    // tilt-series alignment: moments, windowed cross-correlation, resampling
 #include "kernels_bin.hip.h"      // binning of sinograms and volumes by 2 or 4, trilinear prolongation
 #include "kernels_dual.hip.h"     // dual-axis: the volume transposed between two engines with perpendicular tilt axes
+#include "kernels_affine3d.hip.h" // a volume resampled by a 3-D affine map (trilinear, binary64 coordinates)
 #include "kernels_dart.hip.h"     // DART: label / boundary / free-set stencil, masked restore and smoother, per-class sums

@@ -525,6 +525,7 @@ extern "C" {
 #include "engine_align.inc"
 #include "engine_bin.inc"
 #include "engine_dual.inc"
+#include "engine_affine3d.inc"
 #include "engine_dart.inc"
 #include "engine_comm.inc"
 #include "engine_options.inc"

@@ -426,6 +426,7 @@ class _GroupBackend:
 
     c_sino_moments = c_sino_xcorr = c_sino_shift = c_sino_affine = c_sino_axis_profile = _no_align
     c_sino_bin = c_volume_bin = c_volume_prolong = c_volume_cross = c_volume_cross_axpy = _no_align
+    c_volume_affine = c_volume_affine_axpy = _no_align
 
     def c_set_tilt_series(self, ptr):
         self._rows("set_sinogram", SINO_B, ptr, self.nray * self.nproj * 4)
@@ -1173,6 +1174,35 @@ class _EngineBase:
         clamped to 0).  IEEE arithmetic: ``a = 0`` against an Inf gives NaN."""
         partner = self._bin_partner(other)
         check(self.be.L.tomo_volume_cross_axpy(self.be.h, int(src), partner, int(dst), float(a), int(bool(clamp))))
+
+    # ---- a volume resampled by a 3-D affine map (include/tomo_hip.h: tomo_volume_affine / tomo_volume_affine_axpy; the matrix comes
+    # from align.affine_matrix_3d; users: TomoGPU.reorient, DualAxisTomo with a registration) ----------------------------------------
+    @staticmethod
+    def _affine3(M):
+        m = np.ascontiguousarray(M, dtype=np.float64).ravel()
+        if m.shape != (12,):
+            raise ValueError(f"the map must have 12 entries (a row-major 3 x 4 matrix), got shape {np.shape(M)}")
+        if not np.all(np.isfinite(m)):
+            raise ValueError("the map has a non-finite entry")
+        return m
+
+    def volume_affine_to(self, other, M, src=VOL_RECON, dst=VOL_RECON):
+        """Volume ``dst`` of ``other`` = volume ``src`` of this engine resampled trilinearly: ``other[s][y][z] = self(s', y', z')`` with
+        (s', y', z') = ``M`` applied to (s, y, z, 1), ``M`` the 12 float64 entries of a row-major 3 x 4 matrix from a destination voxel
+        to its source position (``align.affine_matrix_3d``); zeros outside the source.  Coordinates in binary64: an identity, a
+        whole-voxel shift, quarter turns and flips copy samples bit for bit.  ``other`` is another whole-volume engine on this device
+        (any size) or this engine itself with ``dst`` != ``src``.  Enqueued on ``other``'s stream, ordered against this engine's by
+        events: no host wait."""
+        m = self._affine3(M)
+        partner = self._bin_partner(other)
+        check(self.be.L.tomo_volume_affine(self.be.h, int(src), partner, int(dst), _ptr(m)))
+
+    def volume_affine_axpy_to(self, other, M, a, clamp=False, src=VOL_RECON, dst=VOL_RECON):
+        """``other[s][y][z] = fma(a, self(s', y', z'), other[s][y][z])``, one rounding, then ``max(0, .)`` with ``clamp`` (a NaN is
+        clamped to 0): the resampled value of ``volume_affine_to`` added in place."""
+        m = self._affine3(M)
+        partner = self._bin_partner(other)
+        check(self.be.L.tomo_volume_affine_axpy(self.be.h, int(src), partner, int(dst), _ptr(m), float(a), int(bool(clamp))))
 
     # ---- DART building blocks (include/tomo_hip.h: tomo_dart_*; the loop is TomoGPU.dart) -----------------------------------------
     def _dart_one_engine(self):

@@ -8,7 +8,7 @@ to the semantics of their canonical loops:
 import numpy as np
 
 from . import _lib, align, pytvlib
-from ._lib import S_DD, S_DIFF2, SINO_B, SINO_G, SINO_PUBLIC, SINO_USER0, VOL_RECON, VOL_USER0, VOL_YK
+from ._lib import S_DD, S_DIFF2, SINO_B, SINO_G, SINO_PUBLIC, SINO_USER0, VOL_RECON, VOL_TEMP, VOL_USER0, VOL_YK
 from .engine import is_tensor, multigpuengine, tomoengine
 
 
@@ -150,6 +150,22 @@ class TomoGPU:
     def cgls(self, Niter=100, show_convergence=True):
         pytvlib.initialize_algorithm(self.tomo, "CGLS")
         return self._run_iterative("CGLS", Niter, show_convergence)
+
+    # ---- positioning the tomogram (an extension: engine.py volume_affine_to; include/tomo_hip.h: tomo_volume_affine) ---------------
+    def reorient(self, rotation_deg=(0, 0, 0), shift=(0, 0, 0), magnification=1.0):
+        """Resample the reconstruction in place by a rigid motion plus scaling (``align.affine_matrix_3d``: rotation about the volume
+        centre by ``rotation_deg`` = (about s, about y, about z), ``magnification``, then ``+shift`` voxels; trilinear, zeros move in
+        from outside), e.g. to take out the pitch of a slab-shaped sample before segmentation or ``dart``.  One interpolation on the
+        device through the scratch volume ``VOL_TEMP`` (the slot of ``copy_recon``), which is clobbered.  Returns the 12 entries of
+        the destination-to-source map it used.  Afterwards the reconstruction is a POSITIONED tomogram: it no longer belongs to the
+        tilt series (its projections are not the data's), so continuing an iterative run from it is the caller's risk.
+        ``ValueError`` for wrong shapes or non-finite values; one whole-volume engine only (``NotImplementedError`` for sharded and
+        sub-slab objects)."""
+        M = align.affine_matrix_3d(rotation_deg, shift, magnification, src_shape=(self.Nslice, self.Nray, self.Nray))
+        t = self._bin_engine()
+        t.volume_affine_to(t, M, src=VOL_RECON, dst=VOL_TEMP)
+        t.be.c("copy_volume", VOL_RECON, VOL_TEMP)
+        return M
 
     # ---- binning and coarse-to-fine reconstruction (an extension: engine.py bin_sinogram_to / prolong_volume_to) ----------------
     def _bin_engine(self):
