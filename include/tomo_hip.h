@@ -318,6 +318,34 @@ int tomo_volume_cross_axpy(tomo_engine *src, int src_vol, tomo_engine *dst, int 
 int tomo_volume_affine(tomo_engine *src, int src_vol, tomo_engine *dst, int dst_vol, const double *m_host /* [12] */);
 int tomo_volume_affine_axpy(tomo_engine *src, int src_vol, tomo_engine *dst, int dst_vol, const double *m_host, float a, int clamp);
 
+/* ---- the 3-D rigid registration of two tomograms: the Gauss-Newton normal equations of one map ----------------------------------
+ * The pose that the two calls above apply is ESTIMATED by minimising sum (G(M x) - F(x))^2 over the six rigid parameters; this call
+ * evaluates, for one map, everything an iteration needs, in one pass over the fixed volume F (the loop itself is 32 numbers of host
+ * arithmetic per iteration: tomo_tv_amd/align.py, register_volumes).  m_host is the destination-to-source map of tomo_volume_affine
+ * with the same convention: the grid of F is the destination, the moving volume G the source, p = M x the position in G of the
+ * voxel x = (s, y, z) of F, by the same chain of fused multiply-adds and the same split into floor and binary32 fraction.
+ * A voxel counts only if (a) all eight tap positions lie inside G, 0 <= floor and floor + 1 <= size - 1 on every axis (stricter than
+ * the zero padding above), and (b) x lies at least `margin` voxels from each face of F.  A voxel that does not count is not read
+ * into anything: an Inf or a NaN in it, or in a voxel of G that is no tap of a counting voxel, stays out of the sums.
+ * Per counting voxel: w = the trilinear value with the arithmetic and tap order stated above; g = (g_s, g_y, g_z) = the gradient of
+ * the trilinear interpolant of the cell at the fractions, in binary32 from the same eight taps -- per component the four tap
+ * differences along that axis, weighted by the products of the two other axes' weights, the first term a product and the three
+ * others fused multiply-adds in ascending order of the two other axes' offsets (the exact order: kernels_register3d.hip.h);
+ * r = w - F(x) and q = p - c_G with c_G = (size - 1) / 2 per axis of G, in binary64;
+ *     J = (g_s, g_y, g_z, q_y g_z - q_z g_y, q_z g_s - q_s g_z, q_s g_y - q_y g_s)   in binary64,
+ * the derivative of G(c_G + Rot(omega)(p - c_G) + t) by (t, omega) at zero.  out_host receives the sums over the counting voxels,
+ * products and accumulation in binary64:  [0..20] the upper triangle of J^T J, row-major;  [21..26] J^T r;  [27] sum r^2;  [28] the
+ * count;  [29..31] sum F^2, sum w^2, sum F w (for a normalised correlation).  No atomics, two stages in a fixed order: the same bits
+ * from call to call.  With no counting voxel every sum is +0.0.
+ * Both volumes are only read: no claim is dropped, and F and G may be two engines, two slots of one engine, or one and the same
+ * slot.  With two engines the kernels run on the fixed engine's stream behind an event of the moving engine's stream, which then
+ * waits for them; the call waits for its result.
+ * TOMO_ERR_ARG: a null engine or pointer, a bad slot, different devices, a non-finite matrix entry, margin < 0 or 2 * margin >= a
+ * size of F.  TOMO_ERR_STATE: an engine bound to a communicator, one that is a slab of a larger volume, or one whose geometry was
+ * released.  A refused call has enqueued nothing and leaves both engines usable. */
+int tomo_volume_affine_normal(tomo_engine *fixed, int fixed_vol, tomo_engine *moving, int moving_vol, const double *m_host /* [12] */,
+                              int margin, double *out_host /* [32] */);   /* waits */
+
 /* ---- DART: discrete tomography for objects made of a few known grey levels ----------------------------------------------------
  * K. J. Batenburg, J. Sijbers, "DART: a practical reconstruction algorithm for discrete tomography", IEEE Trans. Image Process.
  * 20(9), 2011, pp. 2542-2553.  The reference has no DART; these calls are its building blocks on the resident volume, and

@@ -132,6 +132,7 @@ SIGNATURES = {
     "tomo_volume_cross_axpy": [_p, _i, _p, _i, _f, _i],
     "tomo_volume_affine": [_p, _i, _p, _i, _p],
     "tomo_volume_affine_axpy": [_p, _i, _p, _i, _p, _f, _i],
+    "tomo_volume_affine_normal": [_p, _i, _p, _i, _p, _i, _p],
     "tomo_dart_classify": [_p, _i, _p, _i, _i, _u32, _u32],
     "tomo_dart_restore": [_p, _i, _p, _i],
     "tomo_dart_segment": [_p, _i, _p, _i],

@@ -126,6 +126,109 @@ def affine_matrix_3d(rotation_deg=(0, 0, 0), shift=(0, 0, 0), magnification=1.0,
     return M.ravel()
 
 
+# ---- 3-D rigid registration of two volumes: the host side of ``tomoengine.volume_affine_normal`` (32 numbers per iteration) -----------
+def rigid_increment(H, b, damping=0.0):
+    """The Gauss-Newton step ``delta`` = (shift s, y, z; rotation vector s, y, z in radians) of ``(H + damping diag(H)) delta = -b``
+    in binary64.  ``ValueError`` when ``H`` or ``b`` is not finite, ``damping`` is negative, or ``H`` is singular (numerically: a
+    reciprocal condition number below 1e-14) with ``damping`` = 0."""
+    H, b, lam = np.asarray(H, np.float64), np.asarray(b, np.float64), float(damping)
+    if H.shape != (6, 6) or b.shape != (6,):
+        raise ValueError("H must be 6 x 6 and b have 6 entries")
+    if not np.all(np.isfinite(H)) or not np.all(np.isfinite(b)):
+        raise ValueError("the normal equations are not finite")
+    if not lam >= 0.0:
+        raise ValueError("damping must not be negative")
+    A = H + lam * np.diag(np.diag(H))
+    sv = np.linalg.svd(A, compute_uv=False)
+    if not sv[0] > 0.0 or sv[-1] < 1e-14 * sv[0]:
+        if lam == 0.0:
+            raise ValueError("the normal equations are singular: the volumes do not determine all six parameters (try damping > 0)")
+        raise ValueError("the normal equations are singular even with damping: a parameter has no gradient at all")
+    return np.linalg.solve(A, -b)
+
+
+def _rodrigues(omega):
+    """exp of the rotation vector: 1 + sin(t) K + (1 - cos(t)) K^2 with K the cross-product matrix of the unit axis"""
+    w = np.asarray(omega, np.float64)
+    t = float(np.linalg.norm(w))
+    if t == 0.0:
+        return np.eye(3)
+    k = w / t
+    K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    return np.eye(3) + np.sin(t) * K + (1.0 - np.cos(t)) * (K @ K)
+
+
+def compose_rigid_increment(M, delta, src_shape):
+    """The map after a step: ``x -> c + Rot(delta[3:]) (M x - c) + delta[:3]`` with c = (src_shape - 1) / 2, the centre of the moving
+    volume, and ``Rot`` by Rodrigues' formula, so the linear part of a rigid map stays a rotation.  ``delta`` = 0 returns ``M``'s
+    entries unchanged, bit for bit."""
+    m = np.array(M, np.float64).reshape(3, 4)
+    d = np.asarray(delta, np.float64).ravel()
+    c = 0.5 * (np.asarray(src_shape, np.float64).ravel() - 1.0)
+    if d.shape != (6,) or c.shape != (3,) or not np.all(np.isfinite(d)):
+        raise ValueError("delta must be six finite numbers and src_shape three sizes")
+    if not d.any():
+        return m.ravel()
+    Rm = _rodrigues(d[3:])
+    out = np.empty((3, 4))
+    out[:, :3] = Rm @ m[:, :3]
+    out[:, 3] = c + Rm @ (m[:, 3] - c) + d[:3]
+    return out.ravel()
+
+
+def decode_rigid(M, src_shape, dst_shape=None):
+    """``(R, shift)`` with ``affine_matrix_3d(matrix=R, shift=shift, src_shape=..., dst_shape=...) == M``: the content rotation and the
+    shift in voxels of a rigid destination-to-source map."""
+    m = np.asarray(M, np.float64).reshape(3, 4)
+    src = np.asarray(src_shape, np.float64).ravel()
+    dst = src if dst_shape is None else np.asarray(dst_shape, np.float64).ravel()
+    if src.shape != (3,) or dst.shape != (3,) or not np.all(np.isfinite(m)):
+        raise ValueError("M must be 12 finite entries and the shapes three sizes")
+    A = m[:, :3]
+    return A.T.copy(), np.linalg.solve(A, 0.5 * (src - 1.0) - m[:, 3]) - 0.5 * (dst - 1.0)
+
+
+def rotation_angle_deg(Rm):
+    """the angle of a rotation matrix in degrees (from the antisymmetric part and the trace: accurate near 0)"""
+    Rm = np.asarray(Rm, np.float64)
+    s = 0.5 * np.sqrt((Rm[2, 1] - Rm[1, 2]) ** 2 + (Rm[0, 2] - Rm[2, 0]) ** 2 + (Rm[1, 0] - Rm[0, 1]) ** 2)
+    return float(np.rad2deg(np.arctan2(s, 0.5 * (np.trace(Rm) - 1.0))))
+
+
+def register_volumes(fixed, moving, M0=None, max_iter=30, tol_shift=1e-3, tol_deg=1e-3, margin=1, damping=0.0, fixed_vol=0, moving_vol=0):
+    """Intensity-based rigid registration by Gauss-Newton: the map M (12 entries, from a voxel of volume ``fixed_vol`` of engine
+    ``fixed`` to its position in volume ``moving_vol`` of engine ``moving``; ``volume_affine_to``'s convention) that minimises
+    sum (moving(M x) - fixed(x))^2 over the six rigid parameters, from ``M0`` (default: centre onto centre, no rotation).  Every
+    iteration is one ``fixed.volume_affine_normal`` on the device and a 6 x 6 solve here.  Stops when a step is below ``tol_shift``
+    voxels in every component and below ``tol_deg`` degrees, or after ``max_iter`` steps.  -> dict: ``M``; ``R``, ``shift`` (the
+    content rotation and shift of ``affine_matrix_3d`` / ``DualAxisTomo.set_registration``); per evaluation ``ssd``, ``count`` and
+    ``ncc``; per step ``step`` = (largest shift component in voxels, rotation in degrees); ``converged``.  ``RuntimeError`` when
+    fewer than one eighth of the fixed volume's voxels count: the volumes no longer overlap."""
+    fshape, mshape = (fixed.Nslice_, fixed.Ny, fixed.Nz), (moving.Nslice_, moving.Ny, moving.Nz)
+    M = affine_matrix_3d(src_shape=mshape, dst_shape=fshape) if M0 is None else np.array(M0, np.float64).ravel()
+    if M.shape != (12,) or not np.all(np.isfinite(M)):
+        raise ValueError("M0 must be 12 finite entries")
+    if int(max_iter) < 0 or not tol_shift >= 0 or not tol_deg >= 0:
+        raise ValueError("max_iter, tol_shift and tol_deg must not be negative")
+    nvox = fshape[0] * fshape[1] * fshape[2]
+    out = dict(ssd=[], count=[], ncc=[], step=[], converged=False)
+    for _ in range(int(max_iter)):
+        H, b, ssd, count, ncc = fixed.volume_affine_normal(moving, M, margin=margin, fixed_vol=fixed_vol, moving_vol=moving_vol)
+        out["ssd"].append(ssd), out["count"].append(count), out["ncc"].append(ncc)
+        if 8 * count < nvox:
+            raise RuntimeError(f"only {count} of the fixed volume's {nvox} voxels count: the volumes no longer overlap")
+        delta = rigid_increment(H, b, damping)
+        M = compose_rigid_increment(M, delta, mshape)
+        step = (float(np.max(np.abs(delta[:3]))), float(np.rad2deg(np.linalg.norm(delta[3:]))))
+        out["step"].append(step)
+        if step[0] <= tol_shift and step[1] <= tol_deg:
+            out["converged"] = True
+            break
+    out["M"] = M
+    out["R"], out["shift"] = decode_rigid(M, mshape, fshape)
+    return out
+
+
 def axis_score_border(N, search_deg):
     """H = ceil(N/2 sin(search_deg)): a rotation by up to ``search_deg`` about the centre moves a sample of a row of N rays by at most
     that many slices, so the slices H <= s < Nslice - H of the resampled series never hold zero fill"""

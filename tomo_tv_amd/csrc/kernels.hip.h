@@ -22,4 +22,5 @@
 #include "kernels_bin.hip.h"      // binning of sinograms and volumes by 2 or 4, trilinear prolongation
 #include "kernels_dual.hip.h"     // dual-axis: the volume transposed between two engines with perpendicular tilt axes
 #include "kernels_affine3d.hip.h" // a volume resampled by a 3-D affine map (trilinear, binary64 coordinates)
-#include "kernels_dart.hip.h"     // DART: label / boundary / free-set stencil, masked restore and smoother, per-class sums
+#include "kernels_register3d.hip.h" // rigid registration of two volumes: gather, gradient and the 6 x 6 normal equations in one pass
+#include "kernels_dart.hip.h"    // DART: label / boundary / free-set stencil, masked restore and smoother, per-class sums

@@ -293,6 +293,8 @@ struct tomo_engine {
     uint8_t *dart_state = nullptr;
     int dart_nthr = -1;
     double *dart_part = nullptr;
+    // registration (engine_register3d.inc): the workgroups' partial sums of the normal equations [RG_BLOCKS + 1][32] (the last row: the result)
+    double *reg_part = nullptr;
     // scalars
     double *d_scal = nullptr, *d_scal_own = nullptr, *d_part = nullptr, *d_part_aux = nullptr, *d_part_tv = nullptr;
     double *h_snap = nullptr;          // pinned: tomo_scalars_snapshot
@@ -526,6 +528,7 @@ extern "C" {
 #include "engine_bin.inc"
 #include "engine_dual.inc"
 #include "engine_affine3d.inc"
+#include "engine_register3d.inc"
 #include "engine_dart.inc"
 #include "engine_comm.inc"
 #include "engine_options.inc"

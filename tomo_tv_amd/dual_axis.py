@@ -12,8 +12,9 @@ Convention.  The public volume is ``X[s][y][z]``; series A tilts about ``s`` (``
 
 At zero tilt the two series' projections are transposes of each other, ``P_B[z, ray=s] = P_A[s, ray=z]``.  Bringing measured data to
 this convention (mirrors, quarter turns) is the caller's job.  Two measured series are never related by the exact transpose: the
-pose of the second series relative to the first -- a small rigid motion in all three axes -- is APPLIED here
-(``set_registration``, from fiducials or an external registration), not estimated.
+pose of the second series relative to the first -- a small rigid motion in all three axes -- is applied by every driver once it is
+set (``set_registration``, from fiducials or an external registration) or estimated from the two tomograms on the device
+(``estimate_registration``: intensity-based Gauss-Newton, optionally coarse to fine).
 """
 import numpy as np
 
@@ -80,6 +81,47 @@ class DualAxisTomo:
         if self._reg is None:
             return np.eye(3), np.zeros(3)
         return self._reg["R"].copy(), self._reg["shift"].copy()
+
+    def estimate_registration(self, pyramid=(1,), max_iter=30, margin=1, apply=True, **kw):
+        """Estimate the registration from the two tomograms: B's reconstruction is crossed into A's ``VOL_SCRATCH`` and registered
+        onto A's reconstruction by intensity-based Gauss-Newton (``align.register_volumes``: fixed = A's ``VOL_RECON``, moving = the
+        scratch slot), so the result is directly the ``(R, shift)`` of ``set_registration``, ``x_A = T(cross(x_B))``.  BOTH
+        reconstructions must already exist (``dual.a.sirt(..)``, ``dual.b.sirt(..)``, each series on its own): nothing is
+        reconstructed here.  The iteration starts from the registration currently set.  ``pyramid`` lists the binning factors of
+        the levels, falling to 1 -- ``(1,)``, ``(2, 1)``, ``(4, 2, 1)``: a coarser level runs on the binned engine that ``self.a`` keeps per factor
+        (the one ``coarse_to_fine`` uses: built once, its reconstruction is left alone), which receives both volumes in its user
+        slots ``VOL_SCRATCH`` and ``VOL_SAVED`` through ``bin_volume_to``; between levels the shift is scaled by the ratio of the
+        factors and the rotation carried as it is.  ``max_iter`` and ``margin`` hold per level; ``kw`` goes to
+        ``align.register_volumes`` (``tol_shift``, ``tol_deg``, ``damping``).  With ``apply`` the estimate is set
+        (``set_registration(matrix=R, shift=shift)``); without, the object's registration stays as it was (A's ``VOL_SCRATCH`` is
+        overwritten either way).  -> the dict of the finest level, plus ``levels``: the (factor, dict) pairs of every level."""
+        from .align import register_volumes
+        factors = [int(f) for f in pyramid]
+        if not factors or factors[-1] != 1 or any(f not in (1, 2, 4) for f in factors) or any(a <= b for a, b in zip(factors, factors[1:])):
+            raise ValueError("pyramid must list falling factors out of 4, 2, 1 and end with 1: (1,), (2, 1), (4, 1) or (4, 2, 1)")
+        if any(self.N % f for f in factors):
+            raise ValueError(f"N = {self.N} is not divisible by every factor of {tuple(factors)}")
+        ta, tb = self.a.tomo, self.b.tomo
+        Rm, d = self.get_registration()
+        tb.cross_volume_to(ta, src=VOL_RECON, dst=self.VOL_SCRATCH)
+        levels = []
+        for f in factors:
+            n = self.N // f
+            M0 = affine_matrix_3d(shift=d / f, src_shape=(n, n, n), matrix=Rm)
+            if f == 1:
+                res = register_volumes(ta, ta, M0, max_iter=max_iter, margin=margin, fixed_vol=VOL_RECON, moving_vol=self.VOL_SCRATCH, **kw)
+            else:
+                coarse = self.a._coarse(f).tomo
+                ta.bin_volume_to(coarse, f, src=VOL_RECON, dst=self.VOL_SCRATCH)
+                ta.bin_volume_to(coarse, f, src=self.VOL_SCRATCH, dst=self.VOL_SAVED)
+                res = register_volumes(coarse, coarse, M0, max_iter=max_iter, margin=margin, fixed_vol=self.VOL_SCRATCH,
+                                       moving_vol=self.VOL_SAVED, **kw)
+            Rm, d = res["R"], res["shift"] * f
+            levels.append((f, res))
+        out = dict(levels[-1][1], levels=levels)
+        if apply:
+            self.set_registration(matrix=out["R"], shift=out["shift"])
+        return out
 
     # ---- the volume between the two layouts --------------------------------------------------------------------------------------
     def _a_to_b(self):

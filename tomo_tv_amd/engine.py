@@ -426,7 +426,7 @@ class _GroupBackend:
 
     c_sino_moments = c_sino_xcorr = c_sino_shift = c_sino_affine = c_sino_axis_profile = _no_align
     c_sino_bin = c_volume_bin = c_volume_prolong = c_volume_cross = c_volume_cross_axpy = _no_align
-    c_volume_affine = c_volume_affine_axpy = _no_align
+    c_volume_affine = c_volume_affine_axpy = c_volume_affine_normal = _no_align
 
     def c_set_tilt_series(self, ptr):
         self._rows("set_sinogram", SINO_B, ptr, self.nray * self.nproj * 4)
@@ -1203,6 +1203,28 @@ class _EngineBase:
         m = self._affine3(M)
         partner = self._bin_partner(other)
         check(self.be.L.tomo_volume_affine_axpy(self.be.h, int(src), partner, int(dst), _ptr(m), float(a), int(bool(clamp))))
+
+    def volume_affine_normal(self, moving, M, margin=1, fixed_vol=VOL_RECON, moving_vol=VOL_RECON):
+        """The Gauss-Newton normal equations of the rigid registration of volume ``moving_vol`` of ``moving`` (G) onto volume
+        ``fixed_vol`` of this engine (F) at the map ``M`` (12 entries, from a voxel of F to its position in G: the map
+        ``volume_affine_to`` would resample G onto this engine's grid with), in one pass on the device (include/tomo_hip.h:
+        tomo_volume_affine_normal).  A voxel counts when all eight taps lie inside G and it lies ``margin`` voxels inside F.
+        -> ``(H, b, ssd, count, ncc)``: the symmetric 6 x 6 ``J^T J`` and ``J^T r`` for the parameters (shift s, y, z; rotation
+        vector s, y, z in radians, about G's centre), ``ssd`` = sum r^2, the number of counting voxels and the normalised correlation
+        sum F w / sqrt(sum F^2 sum w^2) (0 where that is undefined).  ``moving`` is another whole-volume engine on this device or
+        this engine itself; nothing is written, and the call waits for its 32 numbers."""
+        m = self._affine3(M)
+        if int(margin) < 0:
+            raise ValueError("margin must not be negative")
+        partner = self._bin_partner(moving)
+        out = np.empty(32, np.float64)
+        check(self.be.L.tomo_volume_affine_normal(self.be.h, int(fixed_vol), partner, int(moving_vol), _ptr(m), int(margin), _ptr(out)))
+        H = np.zeros((6, 6))
+        H[np.triu_indices(6)] = out[:21]
+        H = H + np.triu(H, 1).T
+        den = out[29] * out[30]
+        ncc = float(out[31] / np.sqrt(den)) if den > 0.0 else 0.0
+        return H, out[21:27].copy(), float(out[27]), int(out[28]), ncc
 
     # ---- DART building blocks (include/tomo_hip.h: tomo_dart_*; the loop is TomoGPU.dart) -----------------------------------------
     def _dart_one_engine(self):

@@ -251,7 +251,7 @@ class InProcessMultiGPU:
 
     sino_moments = sino_xcorr = sino_shift = sino_affine = sino_axis_profile = _align_one_engine = _no_align
     bin_sinogram_to = bin_volume_to = prolong_volume_to = _no_align      # (two whole-volume engines: engine.py)
-    cross_volume_to = cross_axpy_volume_to = volume_affine_to = volume_affine_axpy_to = _no_align
+    cross_volume_to = cross_axpy_volume_to = volume_affine_to = volume_affine_axpy_to = volume_affine_normal = _no_align
 
     # the reference's own multi-GPU queries (multigpuengine.cpp:385-421)
     def get_gpu_ids(self):
