@@ -214,11 +214,36 @@ int tomo_l1_norm(tomo_engine *e, int vol);                              /* :436 
  *       becomes NaN.  src != dst.
  *   tomo_sino_axis_profile: out_host[a][s] = sum_r X_a[r][s], in binary64 from the first sample, added in a fixed order.  For a
  *       parallel-beam series whose tilt axis runs along s this mass of slice s is the same in every projection a.
+ *   tomo_sino_affine_normal: one Gauss-Newton evaluation of an intensity-based matching of every projection by a shift, an in-plane
+ *       rotation and a magnification, in one pass.  F_a = projection a of fixed_sino (the model), G_a = projection a of moving_sino (the
+ *       series as given); m_host[a] is the destination-to-source map of tomo_sino_affine: sample (r, s) of F_a has the position
+ *       p = (r', s') in G_a, evaluated by the same binary64 chain and split the same way (a fraction that rounds to 1 is the next whole
+ *       pixel with t = 0).  A sample counts when (a) all four tap positions lie inside G_a, 0 <= i and i + 1 <= size - 1 on both axes
+ *       with i the first tap AFTER that split (a coordinate in [-2^-25, 0) is pixel 0 with t = 0 and can count; stricter than the
+ *       zero padding of tomo_sino_affine), and (b) margin <= r <= Nray - 1 - margin and margin <= s <= Nslice - 1 -
+ *       margin.  A sample that does not count loads no tap and adds nothing: an Inf or a NaN there, or in a sample of G that is no tap
+ *       of a counting sample, stays out; padding slices are never read as data.  Per counting sample, in binary32: w = the four-tap
+ *       expression of tomo_sino_affine with every product and every sum rounded once (no fused multiply-add; a zero fraction drops
+ *       its tap, so whole-pixel maps copy bits -- for fractional maps the bits of tomo_sino_affine's own output are NOT promised, since
+ *       that kernel's plain expression is the compiler's to fuse) and (g_r, g_s) = the derivative of the
+ *       bilinear interpolant of the cell, g_r = (1 - ts)(x10 - x00) + ts (x11 - x01), g_s = (1 - tr)(x01 - x00) + tr (x11 - x10), the
+ *       first term a product and the second a fused multiply-add (the exact order: kernels_align_normal.hip.h); at t = 0 the one-sided
+ *       derivative towards the second tap.  Then in binary64: res = w - F, q = p - c_G with c_G = ((Nray - 1) / 2, (Nslice - 1) / 2),
+ *       J = (g_r, g_s, q_r g_s - q_s g_r, q_r g_r + q_s g_s), the derivative of G(c_G + e^lambda Rot(omega)(p - c_G) + t) by
+ *       (t_r, t_s, omega, lambda) at zero.  out_host[a] = the sums over the counting samples of projection a:
+ *       [0..9] the upper triangle of J^T J, row-major;  [10..13] J^T res;  [14] sum res^2;  [15] the count;  [16..18] sum F^2, sum w^2,
+ *       sum F w;  [19..20] sum F, sum w.  With no counting sample all 21 are +0.0, and the other projections are unaffected.  Two
+ *       fixed-order reduction stages, no atomics: the same bits from call to call.  Both slots are only read (no claim on
+ *       TOMO_SINO_G is dropped, no write version moves); fixed_sino == moving_sino is allowed.  Waits for its result.
+ *       TOMO_ERR_ARG also for margin < 0 or 2 * margin >= Nray or Nslice; TOMO_ERR_STATE also for a slab of a larger volume
+ *       (tomo_set_slab_edges) and for released geometry.  A refused call enqueues nothing.
  * TOMO_ERR_ARG: bad slot, src == dst, max_shift out of range, a null pointer, a non-finite shift or matrix entry. */
 int tomo_sino_moments(tomo_engine *e, int sino, double *out_host);      /* [Nproj][3]   logger.py:237-247 */
 int tomo_sino_xcorr(tomo_engine *e, int sino_a, int sino_b, int max_shift, int subtract_mean, double *out_host); /* [Nproj][2S+1][2S+1] */
 int tomo_sino_shift(tomo_engine *e, int src, int dst, const float *shifts_host, int wrap);   /* logger.py:249-250 */
 int tomo_sino_affine(tomo_engine *e, int src, int dst, const double *m_host);                /* [Nproj][6] */
+int tomo_sino_affine_normal(tomo_engine *e, int fixed_sino, int moving_sino, const double *m_host /* [Nproj][6] */, int margin,
+                            double *out_host /* [Nproj][21] */);                             /* waits */
 int tomo_sino_axis_profile(tomo_engine *e, int sino, double *out_host);                      /* [Nproj][Nslice] */
 
 /* ---- binning and prolongation between two engines (coarse-to-fine drivers) --------------------------------------------------
@@ -401,12 +426,12 @@ int tomo_scalars_snapshot(tomo_engine *e);
 int tomo_scalars_snapshot_read(tomo_engine *e, double *out, int count);
 /* Pending work and the other reduction users.  Three things can be in flight between two calls: a tomo_scalars_snapshot not yet read,
  * a tomo_data_distance_sq_async not yet waited for, and the scalars of a tomo_tv_gd_tracked whose read-back the host has deferred
- * (a snapshot).  tomo_dart_classify, tomo_dart_class_stats, tomo_sino_moments, tomo_sino_xcorr and tomo_sino_axis_profile may be called
+ * (a snapshot).  tomo_dart_classify, tomo_dart_class_stats, tomo_sino_moments, tomo_sino_xcorr, tomo_sino_affine_normal and tomo_sino_axis_profile may be called
  * while any of them is: none refuses, none cancels the pending item or changes what it delivers, and both sides deliver what the
  * un-interleaved order delivers, bit for bit.  They run on the engine's stream behind everything enqueued so far; a snapshot is a copy that was
  * enqueued BEFORE them, so it keeps the slot values of that moment (TOMO_S_DART_* of a later classify are not in it); the evaluation
- * on the second stream owns its own partial sums and only TOMO_S_DD, which none of the five writes, and the alignment calls (which
- * may read TOMO_SINO_G) first order the engine's stream behind it.  The five C calls leave the evaluation pending.  tomo_read_scalars, however,
+ * on the second stream owns its own partial sums and only TOMO_S_DD, which none of the six writes, and the alignment calls (which
+ * may read TOMO_SINO_G) first order the engine's stream behind it.  The six C calls leave the evaluation pending.  tomo_read_scalars, however,
  * implies tomo_async_wait, as stated above: a host that fetches TOMO_S_DART_* with it after tomo_dart_classify (the Python wrapper
  * does) has thereby COMPLETED the evaluation -- its TOMO_S_DD is the same value -- and a later tomo_async_wait is a no-op.  Only ONE snapshot can
  * be pending: a second tomo_scalars_snapshot replaces the first. */

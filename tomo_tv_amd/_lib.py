@@ -124,6 +124,7 @@ SIGNATURES = {
     "tomo_sino_xcorr": [_p, _i, _i, _i, _i, _p],
     "tomo_sino_shift": [_p, _i, _i, _p, _i],
     "tomo_sino_affine": [_p, _i, _i, _p],
+    "tomo_sino_affine_normal": [_p, _i, _i, _p, _i, _p],
     "tomo_sino_axis_profile": [_p, _i, _p],
     "tomo_sino_bin": [_p, _i, _p, _i, _i],
     "tomo_volume_bin": [_p, _i, _p, _i, _i],

@@ -3,7 +3,9 @@ matrices of the affine resampling and the score and minimum rule of the tilt-axi
 
 The windows are ``Nangles * (2S+1)^2`` doubles, the matrices ``Nangles * 6`` and the profiles ``Nangles * Nslice``, so this is
 bookkeeping, not hot path: the correlation itself, the moments, the profiles and the resampling are HIP kernels
-(``tomoengine.sino_xcorr`` / ``sino_moments`` / ``sino_axis_profile`` / ``sino_shift`` / ``sino_affine``)."""
+(``tomoengine.sino_xcorr`` / ``sino_moments`` / ``sino_axis_profile`` / ``sino_shift`` / ``sino_affine``).  Likewise the Gauss-Newton
+loops of the 3-D registration and of the per-projection similarity matching: the normal equations are reduced on the device
+(``volume_affine_normal`` / ``sino_affine_normal``), the 6 x 6 and 4 x 4 solves and the composition of the maps happen here."""
 import numpy as np
 
 
@@ -226,6 +228,138 @@ def register_volumes(fixed, moving, M0=None, max_iter=30, tol_shift=1e-3, tol_de
             break
     out["M"] = M
     out["R"], out["shift"] = decode_rigid(M, mshape, fshape)
+    return out
+
+
+# ---- per-projection similarity matching: the host side of ``tomoengine.sino_affine_normal`` (21 numbers per projection and iteration) ----
+_TRIU4 = np.triu_indices(4)
+
+
+def unpack_similarity_normal(out):
+    """``(H, b, ssd, count, ncc)`` from the (Nproj, 21) sums of ``tomo_sino_affine_normal``: H (Nproj, 4, 4) symmetric, b (Nproj, 4),
+    ssd (Nproj,), count (Nproj,) int64 and the mean-subtracted normalised correlation
+    (sum F w - sum F sum w / n) / sqrt((sum F^2 - (sum F)^2 / n)(sum w^2 - (sum w)^2 / n)), 0 where a variance is not positive."""
+    out = np.asarray(out, np.float64).reshape(-1, 21)
+    P = out.shape[0]
+    H = np.zeros((P, 4, 4))
+    H[:, _TRIU4[0], _TRIU4[1]] = out[:, :10]
+    H = H + np.triu(H, 1).transpose(0, 2, 1)
+    n = out[:, 15]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        vf, vw = out[:, 16] - out[:, 19] ** 2 / n, out[:, 17] - out[:, 20] ** 2 / n
+        den = vf * vw
+        good = (n > 0) & (vf > 0.0) & (vw > 0.0) & np.isfinite(den)
+        ncc = np.where(good, (out[:, 18] - out[:, 19] * out[:, 20] / n) / np.sqrt(np.where(good, den, 1.0)), 0.0)
+    return H, out[:, 10:14].copy(), out[:, 14].copy(), n.astype(np.int64), ncc
+
+
+def similarity_increment(H, b, damping=0.0, rotation=True, magnification=True, active=None):
+    """The Gauss-Newton step per projection, ``delta`` (Nproj, 4) = (shift r, shift s, rotation omega in radians, log-magnification
+    lambda), of ``(H + damping diag(H)) delta = -b`` in binary64.  A parameter switched off by ``rotation`` / ``magnification`` is
+    removed from the system (not damped) and its entry of ``delta`` is exactly 0.  ``ValueError``, naming the projection, when ``H``
+    or ``b`` is not finite or the (reduced) ``H`` is singular (numerically: a reciprocal condition number below 1e-14); also when
+    ``damping`` is negative.  ``active`` (Nproj,) bool: a projection outside it is not looked at and gets a zero step (the loop's
+    converged projections: their systems can no longer stop it)."""
+    H, b, lam = np.asarray(H, np.float64), np.asarray(b, np.float64), float(damping)
+    if H.ndim != 3 or H.shape[1:] != (4, 4) or b.shape != (H.shape[0], 4):
+        raise ValueError("H must be (Nproj, 4, 4) and b (Nproj, 4)")
+    if not lam >= 0.0:
+        raise ValueError("damping must not be negative")
+    act = np.ones(H.shape[0], bool) if active is None else np.asarray(active, bool)
+    if act.shape != (H.shape[0],):
+        raise ValueError("active must hold one flag per projection")
+    keep = np.array([0, 1] + ([2] if rotation else []) + ([3] if magnification else []))
+    delta = np.zeros((H.shape[0], 4))
+    for a in np.flatnonzero(act):
+        if not np.all(np.isfinite(H[a])) or not np.all(np.isfinite(b[a])):
+            raise ValueError(f"projection {a}: the normal equations are not finite")
+        A = H[a][np.ix_(keep, keep)]
+        A = A + lam * np.diag(np.diag(A))
+        sv = np.linalg.svd(A, compute_uv=False)
+        if not sv[0] > 0.0 or sv[-1] < 1e-14 * sv[0]:
+            if lam == 0.0:
+                raise ValueError(f"projection {a}: the normal equations are singular: the images do not determine all parameters (try damping > 0)")
+            raise ValueError(f"projection {a}: the normal equations are singular even with damping: a parameter has no gradient at all")
+        delta[a, keep] = np.linalg.solve(A, -b[a, keep])
+    return delta
+
+
+def compose_similarity_increment(M, delta, N, Nslice):
+    """The maps after a step: per projection ``x -> c + e^lambda Rot(omega) (M x - c) + t`` with ``delta`` = (t_r, t_s, omega, lambda),
+    c = ((N-1)/2, (Nslice-1)/2) the centre of the moving image and Rot(omega) = [[cos, -sin], [sin, cos]] in (r, s), so the linear part
+    of a similarity stays a scaled rotation.  A projection whose ``delta`` is all zero keeps its entries of ``M``, bit for bit."""
+    m = np.array(M, np.float64).reshape(-1, 6)
+    d = np.asarray(delta, np.float64).reshape(-1, 4)
+    if d.shape[0] != m.shape[0] or not np.all(np.isfinite(d)):
+        raise ValueError("delta must be four finite numbers per projection")
+    c = np.array([0.5 * (N - 1), 0.5 * (Nslice - 1)])
+    out = m.copy()
+    for a in range(m.shape[0]):
+        if not d[a].any():
+            continue
+        k = np.exp(d[a, 3])
+        S = k * np.array([[np.cos(d[a, 2]), -np.sin(d[a, 2])], [np.sin(d[a, 2]), np.cos(d[a, 2])]])
+        A, t = m[a].reshape(2, 3)[:, :2], m[a].reshape(2, 3)[:, 2]
+        out[a].reshape(2, 3)[:, :2] = S @ A
+        out[a].reshape(2, 3)[:, 2] = c + S @ (t - c) + d[a, :2]
+    return out
+
+
+def decode_similarity(M, N, Nslice):
+    """``(shift (Nproj, 2), rotation_deg (Nproj,), magnification (Nproj,))`` with ``affine_matrices(shift, rotation_deg, magnification,
+    N, Nslice) == M`` for maps whose linear part is a scaled rotation: the inverse of ``affine_matrices``."""
+    m = np.asarray(M, np.float64).reshape(-1, 6)
+    if not np.all(np.isfinite(m)):
+        raise ValueError("M must be finite")
+    c = np.array([0.5 * (N - 1), 0.5 * (Nslice - 1)])
+    P = m.shape[0]
+    shift, rot, mag = np.zeros((P, 2)), np.zeros(P), np.ones(P)
+    for a in range(P):
+        A, t = m[a].reshape(2, 3)[:, :2], m[a].reshape(2, 3)[:, 2]
+        det = A[0, 0] * A[1, 1] - A[0, 1] * A[1, 0]
+        if not det > 0.0:
+            raise ValueError(f"projection {a}: the linear part is not a scaled rotation")
+        mag[a] = 1.0 / np.sqrt(det)
+        rot[a] = np.rad2deg(np.arctan2(A[0, 1] - A[1, 0], A[0, 0] + A[1, 1]))
+        shift[a] = np.linalg.solve(A, c - t) - c
+    return shift, rot, mag
+
+
+def match_projections(eng, fixed, moving, M0=None, max_iter=20, tol_shift=1e-3, tol_deg=1e-3, tol_mag=1e-5, margin=2, damping=0.0,
+                      rotation=True, magnification=True):
+    """Intensity-based matching of every projection by Gauss-Newton: per projection the map M (6 entries, from a sample of slot
+    ``fixed`` to its position in slot ``moving``; ``sino_affine``'s convention) that minimises sum (moving(M x) - fixed(x))^2 over
+    shift, in-plane rotation and magnification, from ``M0`` (default: the identity).  All projections advance together: every
+    iteration is one ``eng.sino_affine_normal`` on the device and a 4 x 4 solve per projection here.  A projection stops when a step
+    is below ``tol_shift`` pixels in both components, ``tol_deg`` degrees and ``tol_mag`` in log-magnification, and keeps its map from
+    then on; the loop ends when all have, or after ``max_iter`` steps.  -> dict: ``M`` (Nproj, 6); ``shift``, ``rotation_deg``,
+    ``magnification`` (``decode_similarity``: what ``affine_matrices`` / ``set_alignment`` take); per evaluation ``ssd``, ``count``,
+    ``ncc`` (each (Nproj,)); per step ``step`` (Nproj, 3) = (largest shift component, rotation in degrees, |log-magnification|);
+    ``converged`` (Nproj,) bool.  ``RuntimeError``, naming the projections, when fewer than one eighth of a projection's samples count."""
+    P, N, ns = eng.Nproj, eng.Ny, eng.Nslice_
+    M = np.tile(np.array([1.0, 0, 0, 0, 1.0, 0]), (P, 1)) if M0 is None else np.array(M0, np.float64).reshape(-1, 6)
+    if M.shape != (P, 6) or not np.all(np.isfinite(M)):
+        raise ValueError(f"M0 must be {(P, 6)} finite entries")
+    if int(max_iter) < 0 or not tol_shift >= 0 or not tol_deg >= 0 or not tol_mag >= 0:
+        raise ValueError("max_iter and the tolerances must not be negative")
+    out = dict(ssd=[], count=[], ncc=[], step=[])
+    done = np.zeros(P, bool)
+    for _ in range(int(max_iter)):
+        H, b, ssd, count, ncc = eng.sino_affine_normal(fixed, moving, M, margin=margin)
+        out["ssd"].append(ssd), out["count"].append(count), out["ncc"].append(ncc)
+        few = np.flatnonzero(8 * count < N * ns)
+        if few.size:
+            raise RuntimeError(f"projections {few.tolist()}: fewer than one eighth of the {N * ns} samples count: the images no longer overlap")
+        delta = similarity_increment(H, b, damping, rotation, magnification, active=~done)
+        M = compose_similarity_increment(M, delta, N, ns)
+        step = np.stack([np.max(np.abs(delta[:, :2]), axis=1), np.rad2deg(np.abs(delta[:, 2])), np.abs(delta[:, 3])], axis=1)
+        out["step"].append(step)
+        done = done | ((step[:, 0] <= tol_shift) & (step[:, 1] <= tol_deg) & (step[:, 2] <= tol_mag))
+        if done.all():
+            break
+    out["converged"] = done
+    out["M"] = M
+    out["shift"], out["rotation_deg"], out["magnification"] = decode_similarity(M, N, ns)
     return out
 
 

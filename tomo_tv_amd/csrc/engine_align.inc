@@ -1,6 +1,6 @@
 // engine_align.inc -- tilt-series alignment: per-angle moments, windowed cross-correlation, resampling by per-angle shifts or affine
-// maps, per-slice mass profiles.
-// Part of tomo_engine.hip (included inside its extern "C" block, after engine_api.inc); kernels: kernels_align.hip.h.
+// maps, the normal equations of a per-projection similarity matching, per-slice mass profiles.
+// Part of tomo_engine.hip (included inside its extern "C" block, after engine_api.inc); kernels: kernels_align.hip.h, kernels_align_normal.hip.h.
 //
 // One whole-volume engine only: a shift along the tilt axis moves samples across slab boundaries, so an engine bound to a
 // communicator refuses (TOMO_ERR_STATE).  The buffers (partial sums, moments, means, the window) belong to the engine's registry and
@@ -132,6 +132,42 @@ int tomo_sino_affine(tomo_engine *e, int src, int dst, const double *m_host)
     hipLaunchKernelGGL(k_sino_affine, dim3(blocks, e->np), dim3(256), 0, e->stream, (const float *)s, d, (const double *)e->stage, e->n, e->nx, e->sx);
     LAUNCHCHK();
     HIPCHK(hipStreamSynchronize(e->stream));        // the table is read from the caller's host memory
+    return TOMO_OK;
+}
+
+// a sinogram slot that is only read (engine_bin.inc): asking for G does not drop its claim
+static int sino_slot_ro(tomo_engine *e, int id, float **out);
+
+// The Gauss-Newton normal equations of every projection (kernels_align_normal.hip.h).  Everything that can be refused is refused before
+// anything is enqueued.  Both slots are read-only views: no claim is dropped, no version moves, and they may be one slot.  The
+// workgroups' partial sums go to al_part, the result to al_out with the matrices behind it ([np][21] then [np][6] doubles): every
+// entry that is read was written by the same call.  The call waits for its 21 * np numbers.
+int tomo_sino_affine_normal(tomo_engine *e, int fixed_sino, int moving_sino, const double *m_host, int margin, double *out_host)
+{
+    NEED_ALIGN(e);
+    if (!m_host) return fail(TOMO_ERR_ARG, "null matrices");
+    if (!out_host) return fail(TOMO_ERR_ARG, "null output");
+    if (fixed_sino < 0 || fixed_sino >= TOMO_SINO_SLOTS || moving_sino < 0 || moving_sino >= TOMO_SINO_SLOTS) return fail(TOMO_ERR_ARG, "bad sinogram id");
+    for (int i = 0; i < 6 * e->np; ++i) if (!std::isfinite(m_host[i])) return fail(TOMO_ERR_ARG, "non-finite matrix entry");
+    if (margin < 0) return fail(TOMO_ERR_ARG, "negative margin");
+    if (2 * (int64_t)margin >= std::min(e->n, e->nx)) return fail(TOMO_ERR_ARG, "the margin leaves no sample of a projection (2 * margin >= a size)");
+    if (!(e->is_first && e->is_last)) return fail(TOMO_ERR_STATE, "alignment runs on one whole-volume engine: this engine is a slab of a larger volume (tomo_set_slab_edges)");
+    { int rc_ = order_after_async(e); if (rc_) return rc_; }
+    float *f, *g; int rc;
+    if ((rc = sino_slot_ro(e, fixed_sino, &f)) || (rc = sino_slot_ro(e, moving_sino, &g))) return rc;
+    const int nblk = (e->n + SN_ROWS - 1) / SN_ROWS;
+    if ((rc = al_ensure(e, (void **)&e->al_part, &e->al_part_bytes, (size_t)e->np * nblk * SN_SUMS * sizeof(double)))) return rc;
+    if ((rc = al_ensure(e, (void **)&e->al_out, &e->al_out_bytes, (size_t)e->np * (SN_SUMS + 6) * sizeof(double)))) return rc;
+    double *mat = e->al_out + (size_t)e->np * SN_SUMS;
+    HIPCHK(hipMemcpyAsync(mat, m_host, (size_t)e->np * 6 * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(k_sino_affine_normal, dim3(nblk, e->np), dim3(256), 0, e->stream, (const float *)f, (const float *)g, (const double *)mat,
+                       e->n, e->nx, e->sx, margin, e->al_part);
+    LAUNCHCHK();
+    hipLaunchKernelGGL(k_sino_affine_normal_finish, dim3((e->np * SN_SUMS + 255) / 256), dim3(256), 0, e->stream, (const double *)e->al_part,
+                       e->al_out, e->np, nblk);
+    LAUNCHCHK();
+    HIPCHK(hipMemcpyAsync(out_host, e->al_out, (size_t)e->np * SN_SUMS * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));       // the matrices are read from the caller's host memory
     return TOMO_OK;
 }
 

@@ -424,7 +424,7 @@ class _GroupBackend:
     def _no_align(self, *a):
         raise NotImplementedError("alignment runs on one whole-volume engine: a shift along the tilt axis crosses the sub-slabs")
 
-    c_sino_moments = c_sino_xcorr = c_sino_shift = c_sino_affine = c_sino_axis_profile = _no_align
+    c_sino_moments = c_sino_xcorr = c_sino_shift = c_sino_affine = c_sino_axis_profile = c_sino_affine_normal = _no_align
     c_sino_bin = c_volume_bin = c_volume_prolong = c_volume_cross = c_volume_cross_axpy = _no_align
     c_volume_affine = c_volume_affine_axpy = c_volume_affine_normal = _no_align
 
@@ -1112,6 +1112,28 @@ class _EngineBase:
         if m.shape != (self.Nproj, 6):
             raise ValueError(f"matrices must have shape {(self.Nproj, 6)}, got {m.shape}")
         self.be.c("sino_affine", int(src), int(dst), _ptr(m))
+
+    def sino_affine_normal(self, fixed, moving, matrices, margin=1):
+        """The Gauss-Newton normal equations of the matching of every projection of sinogram slot ``moving`` (G, the series as given)
+        onto the same projection of slot ``fixed`` (F, the model) at the maps ``matrices`` = (Nproj, 6) float64, ``sino_affine``'s
+        convention (from a sample of F to its position in G), in one pass on the device (include/tomo_hip.h:
+        tomo_sino_affine_normal).  A sample counts when all four taps lie inside G and it lies ``margin`` pixels inside F.
+        -> ``(H, b, ssd, count, ncc)``: per projection the symmetric 4 x 4 ``J^T J`` and ``J^T r`` for the parameters (shift r, shift s,
+        rotation in radians, log-magnification, about G's centre), ``ssd`` = sum r^2, the number of counting samples and the
+        mean-subtracted normalised correlation of F and the resampled G over them (0 where that is undefined).  Nothing is written;
+        the call waits for its 21 numbers per projection."""
+        self._align_one_engine()
+        m = np.ascontiguousarray(matrices, dtype=np.float64)
+        if m.shape != (self.Nproj, 6):
+            raise ValueError(f"matrices must have shape {(self.Nproj, 6)}, got {m.shape}")
+        if not np.all(np.isfinite(m)):
+            raise ValueError("a matrix has a non-finite entry")
+        if int(margin) < 0 or 2 * int(margin) >= min(self.Ny, self.Nslice_):
+            raise ValueError("margin must not be negative and 2 * margin must stay below Nray and Nslice")
+        out = np.empty((self.Nproj, 21), np.float64)
+        self.be.c("sino_affine_normal", int(fixed), int(moving), _ptr(m), int(margin), _ptr(out))
+        from .align import unpack_similarity_normal
+        return unpack_similarity_normal(out)
 
     def sino_axis_profile(self, which=SINO_B):
         """(Nproj, Nslice) float64: c_p[s] = sum_r X_p[r][s] of sinogram slot ``which``, the mass of slice s seen by projection p --

@@ -559,6 +559,59 @@ class TomoGPU:
                 shifts = self._align_pass(t, f, shifts, max_shift, recon, subpixel, leave_one_out, loo_iters)
         return self.get_alignment()
 
+    def refine_alignment_affine(self, Nouter=3, recon=None, rotation=True, magnification=True, leave_one_out=False, loo_iters=20,
+                                max_iter=20, margin=2, damping=0.0):
+        """Projection matching by intensity: per projection a shift, an in-plane rotation and a magnification, estimated by
+        Gauss-Newton on the device (``align.match_projections``, ``tomoengine.sino_affine_normal``).  Every outer pass reconstructs
+        (``recon(self)``; default 20 SIRT iterations; or with ``leave_one_out`` the model of ``refine_alignment``, ``loo_iters`` SIRT
+        iterations that never saw the projection), projects the result and matches the series AS GIVEN (``ALIGN_SLOT``) to that model,
+        starting from the stored shifts, rotation and magnification (``align.affine_matrices``).  Three gauges are removed from the
+        result: the mean of ds (a translation of the volume along the tilt axis, as in ``refine_alignment``); the mean of the
+        rotation increment of the pass (a common in-plane rotation is the tilt-axis direction: ``estimate_tilt_axis_rotation`` finds
+        it); the mean of the log-magnification increment (a common magnification only rescales the volume).  The new totals are
+        stored and the series as given is resampled ONCE by them; ``get_alignment()`` / ``get_alignment_rotation()`` report them.
+        ``rotation=False`` / ``magnification=False`` remove that parameter from the fit: its stored values stay bit-identical.
+        Returns ``(shifts, rotation_deg, magnification)``; ``self.align_affine_history`` holds that triple after every pass and
+        ``self.align_affine_cost`` per pass a dict of the per-evaluation ``ssd`` and ``ncc`` and of ``converged``.
+
+        Capture range: the matching follows the image gradient, so it finds a distortion of about a pixel, a few at most, at the
+        image border (a rotation of 1 degree moves the border of a 512-pixel image by 4.5 pixels); there is no pyramid.  Run it
+        after ``align_center_of_mass`` / ``refine_alignment`` have brought the shifts within that range.  With few projections the
+        plain form stalls as ``refine_alignment``'s does: use ``leave_one_out``."""
+        t = self._align_engine()
+        if leave_one_out and recon is not None:
+            raise ValueError("leave_one_out reconstructs by itself (loo_iters SIRT iterations): recon is not used")
+        if recon is None:
+            recon = lambda rec: rec.sirt(20, show_convergence=False)  # noqa: E731
+        shifts = self.get_alignment()
+        self.align_affine_history, self.align_affine_cost = [], []
+        for _ in range(int(Nouter)):
+            if leave_one_out:
+                model = self._model_leave_one_out(loo_iters)
+            else:
+                recon(self)
+                t.forward_projection()
+                model = SINO_G
+            rot, mag = self.get_alignment_rotation()
+            M0 = align.affine_matrices(shifts, rot, mag, self.Nray, self.Nslice)
+            res = align.match_projections(t, model, self.ALIGN_SLOT, M0, max_iter=max_iter, margin=margin, damping=damping,
+                                          rotation=rotation, magnification=magnification)
+            shifts = res["shift"].copy()
+            shifts[:, 1] -= shifts[:, 1].mean()
+            if rotation:
+                drot = res["rotation_deg"] - rot
+                rot = rot + (drot - drot.mean())
+            if magnification:
+                dlog = np.log(res["magnification"]) - np.log(mag)
+                mag = mag * np.exp(dlog - dlog.mean())
+            if rotation or magnification:
+                self._align_rot = (rot, mag)
+            self._align_resample(t, shifts)
+            self._align_shifts = shifts.copy()
+            self.align_affine_history.append((shifts.copy(), rot.copy(), mag.copy()))
+            self.align_affine_cost.append(dict(ssd=res["ssd"], ncc=res["ncc"], converged=res["converged"]))
+        return self.get_alignment(), *self.get_alignment_rotation()
+
     # ---- DART: discrete tomography (an extension; Batenburg & Sijbers 2011; engine.py dart_*) -------------------------------------
     def _dart_engine(self):
         t = self.tomo
