@@ -123,6 +123,31 @@ def test_axis_profile(case):
     assert np.array_equal(c, case.eng.sino_axis_profile(A_SLOT))
 
 
+def test_sums_over_several_workgroups_per_projection(gpu):
+    """Nray = 72 with 5 slices and 2 angles: two workgroups per projection for the profile (64 rays each), three for the moments (32)
+    and five for the normal equations (16), the last one partial every time, so the second stage adds more than one row per output.
+    The statements and bounds are those of the tests of each call: test_axis_profile, test_gpu_align.py (moments) and
+    test_gpu_sino_normal.py (ref64_sino_normal.bound, the exact count)."""
+    import ref64_sino_normal as SN
+    c = Case((5, 72, 2))
+    prof, ref = c.eng.sino_axis_profile(A_SLOT), F.profile(c.A)
+    assert prof.shape == (c.P, c.ns) and np.all(np.abs(prof - ref) <= 1e-12 * np.abs(ref))
+    assert np.array_equal(prof, c.eng.sino_axis_profile(A_SLOT))
+    m, ref = c.eng.sino_moments(A_SLOT), RA.moments(c.A)
+    assert m.shape == (c.P, 3) and np.all(np.abs(m - ref) <= 1e-6 * np.abs(ref))
+    assert np.array_equal(m, c.eng.sino_moments(A_SLOT))
+    Fx = np.random.default_rng(72).random((c.P, c.N, c.ns), dtype=np.float32)
+    c.put(D_SLOT, Fx)
+    M = np.array([[1.0, 0, 0, 0, 1.0, 0], F.matrices([[0.3, -0.6]], 1.3, 1.02, c.N, c.ns)[0]])
+    for margin in (0, 1):
+        ref, bnd, _ = SN.bound(Fx, c.A, M, margin)
+        got = np.full((c.P, 21), np.nan)
+        c.eng.be.c("sino_affine_normal", D_SLOT, A_SLOT, M.ctypes.data_as(ctypes.c_void_p), margin, got.ctypes.data_as(ctypes.c_void_p))
+        r = SN.ratios(got, ref, bnd)
+        print(f"margin {margin}: worst error / bound per projection {np.round(r.max(axis=1), 4)}, samples that count {ref[:, 15].astype(int)}")
+        assert np.array_equal(got[:, 15], ref[:, 15]) and np.all(ref[:, 15] > 0) and r.max() <= 1.0
+
+
 def test_refusals_leave_the_engine_usable(case):
     from tomo_tv_amd import _lib
     L, h, P = case.eng.be.L, case.eng.be.h, case.P

@@ -173,11 +173,9 @@ def test_smooth(case):
     assert np.array_equal(e.get_volume(V1).view(np.uint32), y.view(np.uint32))
 
 
-@pytest.mark.parametrize("nthr", [0, 1, 3, 15])
-def test_class_stats(case, nthr):
-    e = case.eng
+def check_class_stats(e, shape, nthr):
     thr = np.asarray(THR[nthr], np.float32)
-    x = volume(case.shape, 17 + nthr, thr)
+    x = volume(shape, 17 + nthr, thr)
     e.set_volume(x, V0)
     got, again, want = e.dart_class_stats(thr, V0), e.dart_class_stats(thr, V0), R.class_stats(x, thr)
     assert np.array_equal(got[:, 1], want[:, 1])
@@ -187,6 +185,18 @@ def test_class_stats(case, nthr):
         tol = want[c, 1] * 2.0 ** -53 * np.abs(x[fin & (lab == c)].astype(np.float64)).sum()
         assert abs(got[c, 0] - want[c, 0]) <= tol, (c, got[c, 0], want[c, 0], tol)
     assert np.array_equal(got.view(np.uint64), again.view(np.uint64))
+
+
+@pytest.mark.parametrize("nthr", [0, 1, 3, 15])
+def test_class_stats(case, nthr):
+    check_class_stats(case.eng, case.shape, nthr)
+
+
+@pytest.mark.parametrize("nthr", [1, 15])
+def test_class_stats_with_more_than_256_workgroups(gpu, nthr):
+    """One slice of 65 x 65 is 4225 rows of pitch 64, 265 workgroups of 1024 floats: the smallest volume at which a thread of the
+    second stage (256 threads per output) adds more than one of the workgroups' rows.  The statement and the bound of test_class_stats."""
+    check_class_stats(engine(1, 65, 2), (1, 65, 65), nthr)
 
 
 def test_refusals(small):

@@ -20,6 +20,7 @@ pytestmark = pytest.mark.gpu
 
 SHAPES = [((8, 8, 8), (8, 8, 8)), ((40, 40, 40), (40, 40, 40)), ((70, 70, 70), (70, 70, 70)), ((130, 130, 130), (130, 130, 130)),
           ((5, 12, 12), (9, 10, 10))]
+FLAT = (8, 48, 48)                            # 8 slices x 48 x 48: 288 blocks of AF_ROWS rows, so 288 workgroups' rows for the 256 threads of the second stage
 V0, V1, V2 = 5, 6, 7                          # TOMO_VOL_USER0 ..
 ANG_A, ANG_B = np.linspace(-60, 60, 2), np.linspace(-50, 40, 3)
 ARG, STATE = 1, 3
@@ -93,6 +94,20 @@ def test_sums_against_binary64(pair, name):
             H2, b2, ssd2, count2, ncc2 = G3.unpack(got)
             assert np.array_equal(H, H2) and np.array_equal(H, H.T) and np.array_equal(b, b2) and (ssd, count, ncc) == (ssd2, count2, ncc2)
     print(f"{pair.src} onto {pair.dst}, {name}: worst error / bound over the margins and the 32 sums {worst:.4f}")
+
+
+def test_sums_with_more_rows_than_threads_in_the_second_stage(gpu):
+    """``FLAT`` against itself: the smallest pair at which a thread of the second stage adds more than one of the workgroups' rows with
+    few voxels per workgroup.  The statement and the bounds of test_sums_against_binary64, margins 0 and 1."""
+    p = Pair(FLAT, FLAT)
+    for name, M in p.maps().items():
+        for margin, (ref, bnd, summ) in G3.evaluate(p.Fv, p.Gv, M, (0, 1)).items():
+            got = raw(p.b, V1, p.a, V0, M, margin)
+            r = G3.ratios(got, ref, bnd)
+            assert got[28] == ref[28] and ref[28] > 0 and r.max() <= 1.0, (name, margin, int(r.argmax()), r.max())
+            if name != "general":
+                assert np.all(np.abs(got[29:] - ref[29:]) <= summ[29:]), (name, margin)
+        assert np.array_equal(got.view(np.uint64), raw(p.b, V1, p.a, V0, M, margin).view(np.uint64))
 
 
 def test_one_engine_with_two_slots_equals_two_engines(pair):

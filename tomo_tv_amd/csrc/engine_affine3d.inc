@@ -2,26 +2,21 @@
 // (tomo_volume_affine, tomo_volume_affine_axpy).
 // Part of tomo_engine.hip (included inside its extern "C" block, after engine_dual.inc); kernel: kernels_affine3d.hip.h.
 //
-// Whole-volume engines on one device (the NEED_ALIGN rule, and neither may be a slab of a larger volume: the taps of a slab's
-// boundary voxels live on its neighbours).  The sizes of the two engines are free.  Refusal, slot bookkeeping and ordering are those
-// of engine_dual.inc: everything that can be refused is refused before anything is enqueued or any engine state is touched; with two
-// engines the kernel runs on the destination's stream behind an event of the source's, and the source's stream then waits for the
-// kernel; with one engine both fences fall away and the kernel runs on its stream alone.  The matrix travels as a kernel argument:
-// no staging buffer, no host wait.
+// Whole-volume engines on one device; neither may be a slab of a larger volume: the taps of a slab's boundary voxels live on its
+// neighbours.  The sizes of the two engines are free.  Refusal, slot bookkeeping and ordering: the pair rules of engine_bin.inc; with
+// one engine both fences fall away and the kernel runs on its stream alone.  The matrix travels as a kernel argument: no staging
+// buffer, no host wait.
 
 static int affine3d_pair(tomo_engine *src, tomo_engine *dst, int src_vol, int dst_vol, const double *m_host)
 {
-    if (!src || !dst) return fail(TOMO_ERR_ARG, "null engine");
+    const Pair p{src, dst, src_vol, dst_vol, false, "resampling"};
+    if (int rc = pair_check(p, PAIR_ENGINES)) return rc;
     if (!m_host) return fail(TOMO_ERR_ARG, "null matrix");
-    if (src_vol < 0 || src_vol >= TOMO_VOL_SLOTS || dst_vol < 0 || dst_vol >= TOMO_VOL_SLOTS) return fail(TOMO_ERR_ARG, "bad volume id");
+    if (int rc = pair_check(p, PAIR_SLOTS)) return rc;
     if (src == dst && src_vol == dst_vol) return fail(TOMO_ERR_ARG, "within one engine the source and the destination must be two slots");
-    if (src->device != dst->device) return fail(TOMO_ERR_ARG, "the engines live on different devices");
+    if (int rc = pair_check(p, PAIR_DEVICE)) return rc;
     for (int i = 0; i < 12; ++i) if (!std::isfinite(m_host[i])) return fail(TOMO_ERR_ARG, "non-finite matrix entry");
-    NEED_ALIGN(src);
-    NEED_ALIGN(dst);
-    if (!(src->is_first && src->is_last) || !(dst->is_first && dst->is_last))
-        return fail(TOMO_ERR_STATE, "resampling needs whole volumes: an engine is a slab of a larger one (tomo_set_slab_edges)");
-    return TOMO_OK;
+    return pair_check(p, PAIR_STATE);
 }
 
 static int affine3d_launch(bool axpy, tomo_engine *src, int src_vol, tomo_engine *dst, int dst_vol, const double *m_host, float a, int clamp)

@@ -17,8 +17,36 @@ static int al_ensure(tomo_engine *e, void **p, size_t *have, size_t bytes)
 
 #define NEED_ALIGN(e) do { NEED(e); if ((e)->comm) return fail(TOMO_ERR_STATE, "alignment runs on one whole-volume engine: this engine has a communicator"); } while (0)
 
-// moments of sinogram g into al_mom[which] ([np][3] doubles) and its means into al_mean[which] ([np] floats); enqueued, no wait
-static int al_moments(tomo_engine *e, const float *g, int which)
+// a sinogram slot that is only read: allocated (zero) on first use like any slot, but asking for G does not drop its claim
+static int sino_slot_ro(tomo_engine *e, int id, float **out)
+{
+    if (id < 0 || id >= TOMO_SINO_SLOTS) return fail(TOMO_ERR_ARG, "bad sinogram id");
+    if (!e->sino[id]) { int rc = dev_alloc(e, GEOMETRY, (void **)&e->sino[id], e->sino_elems() * sizeof(float), true); if (rc) return rc; }
+    *out = e->sino[id];
+    return TOMO_OK;
+}
+
+// The tail of every call that sums in two stages (kernels_geom.hip.h) and hands the result to the caller: the second stage (finish()
+// launches it on e's stream) behind a first stage that was launched well, the copy of the result to the caller's memory, and the wait
+// for it.  With a partner the first stage read a volume of another engine: the fence back to the partner's stream follows the
+// launches and goes back even when one of them failed.
+extern "C++" {
+template <class Finish>
+static int reduce_tail(Finish &&finish, tomo_engine *e, const double *dev, double *host, size_t bytes, hipError_t launched = hipSuccess,
+                       tomo_engine *partner = nullptr)
+{
+    if (launched == hipSuccess) { finish(); launched = hipGetLastError(); }
+    const int rc = partner ? io_fence(e, e->stream, partner->stream) : TOMO_OK;
+    HIPCHK(launched);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return TOMO_OK;
+}
+}
+
+// the moments of sinogram g, first stage: the workgroups' triples into al_part; enqueued, no wait
+static int al_moments_part(tomo_engine *e, const float *g)
 {
     const int nblk = (e->n + AL_MROWS - 1) / AL_MROWS;
     int rc;
@@ -27,8 +55,22 @@ static int al_moments(tomo_engine *e, const float *g, int which)
     if (!e->al_mean) { if ((rc = dev_alloc(e, GEOMETRY, (void **)&e->al_mean, (size_t)2 * e->np * sizeof(float), false))) return rc; }
     hipLaunchKernelGGL(k_sino_moments, dim3(nblk, e->np), dim3(256), 0, e->stream, g, e->al_part, e->n, e->nx, e->sx);
     LAUNCHCHK();
-    hipLaunchKernelGGL(k_sino_moments_finish, dim3((e->np * 3 + 255) / 256), dim3(256), 0, e->stream, (const double *)e->al_part,
-                       e->al_mom + (size_t)which * e->np * 3, e->al_mean + (size_t)which * e->np, e->np, nblk, (double)e->n * (double)e->nx);
+    return TOMO_OK;
+}
+
+// second stage: the moments into al_mom[which] ([np][3] doubles) and the means into al_mean[which] ([np] floats), in the one launch
+static void al_moments_finish(tomo_engine *e, int which)
+{
+    hipLaunchKernelGGL(k_sum_rows_ascending, dim3((e->np * 3 + 255) / 256), dim3(256), 0, e->stream, (const double *)e->al_part,
+                       e->al_mom + (size_t)which * e->np * 3, e->np, (e->n + AL_MROWS - 1) / AL_MROWS, 3, e->al_mean + (size_t)which * e->np,
+                       (double)e->n * (double)e->nx);
+}
+
+// both stages; enqueued, no wait
+static int al_moments(tomo_engine *e, const float *g, int which)
+{
+    if (int rc = al_moments_part(e, g)) return rc;
+    al_moments_finish(e, which);
     LAUNCHCHK();
     return TOMO_OK;
 }
@@ -39,10 +81,8 @@ int tomo_sino_moments(tomo_engine *e, int sino, double *out_host)
     if (!out_host) return fail(TOMO_ERR_ARG, "null output");
     { int rc_ = order_after_async(e); if (rc_) return rc_; }
     float *g; int rc;
-    if ((rc = sino_slot(e, sino, &g)) || (rc = al_moments(e, g, 0))) return rc;
-    HIPCHK(hipMemcpyAsync(out_host, e->al_mom, (size_t)e->np * 3 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return TOMO_OK;
+    if ((rc = sino_slot(e, sino, &g)) || (rc = al_moments_part(e, g))) return rc;
+    return reduce_tail([&] { al_moments_finish(e, 0); }, e, e->al_mom, out_host, (size_t)e->np * 3 * sizeof(double));
 }
 
 int tomo_sino_xcorr(tomo_engine *e, int sino_a, int sino_b, int max_shift, int subtract_mean, double *out_host)
@@ -68,14 +108,12 @@ int tomo_sino_xcorr(tomo_engine *e, int sino_a, int sino_b, int max_shift, int s
     else if (smax == 8) hipLaunchKernelGGL((k_sino_xcorr<8, 9, 9>), grid, block, 0, e->stream, A, B, mA, mB, e->al_part, e->n, e->nx, e->sx, nchunk);
     else hipLaunchKernelGGL((k_sino_xcorr<16, 11, 11>), grid, block, 0, e->stream, A, B, mA, mB, e->al_part, e->n, e->nx, e->sx, nchunk);
     LAUNCHCHK();
-    hipLaunchKernelGGL(k_sino_xcorr_finish, dim3((e->np * w * w + 255) / 256), dim3(256), 0, e->stream, (const double *)e->al_part, e->al_out,
-                       e->np, nblk, smax, S);
-    LAUNCHCHK();
-    HIPCHK(hipMemcpyAsync(out_host, e->al_out, (size_t)e->np * w * w * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return TOMO_OK;
+    return reduce_tail([&] { hipLaunchKernelGGL(k_sino_xcorr_finish, dim3((e->np * w * w + 255) / 256), dim3(256), 0, e->stream,
+                                                (const double *)e->al_part, e->al_out, e->np, nblk, smax, S); },
+                       e, e->al_out, out_host, (size_t)e->np * w * w * sizeof(double));
 }
 
+// The axis split of kernels_geom.hip.h on the host, applied to -d, with the wrap and the pin of k that only this call needs:
 // -d = k + t with k = floor(-d) and t in [0, 1).  k and the binary64 fraction are exact (d is a binary32 number); rounded to binary32
 // the fraction of a tiny positive d (1 - 2^-30, say) becomes 1, which is the whole-pixel shift k + 1 and is passed on as such, so
 // that the kernel's copy path takes it -- never a two-tap form with weights 0 and 1.  Without wrap a k beyond the image on either
@@ -135,9 +173,6 @@ int tomo_sino_affine(tomo_engine *e, int src, int dst, const double *m_host)
     return TOMO_OK;
 }
 
-// a sinogram slot that is only read (engine_bin.inc): asking for G does not drop its claim
-static int sino_slot_ro(tomo_engine *e, int id, float **out);
-
 // The Gauss-Newton normal equations of every projection (kernels_align_normal.hip.h).  Everything that can be refused is refused before
 // anything is enqueued.  Both slots are read-only views: no claim is dropped, no version moves, and they may be one slot.  The
 // workgroups' partial sums go to al_part, the result to al_out with the matrices behind it ([np][21] then [np][6] doubles): every
@@ -163,12 +198,9 @@ int tomo_sino_affine_normal(tomo_engine *e, int fixed_sino, int moving_sino, con
     hipLaunchKernelGGL(k_sino_affine_normal, dim3(nblk, e->np), dim3(256), 0, e->stream, (const float *)f, (const float *)g, (const double *)mat,
                        e->n, e->nx, e->sx, margin, e->al_part);
     LAUNCHCHK();
-    hipLaunchKernelGGL(k_sino_affine_normal_finish, dim3((e->np * SN_SUMS + 255) / 256), dim3(256), 0, e->stream, (const double *)e->al_part,
-                       e->al_out, e->np, nblk);
-    LAUNCHCHK();
-    HIPCHK(hipMemcpyAsync(out_host, e->al_out, (size_t)e->np * SN_SUMS * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));       // the matrices are read from the caller's host memory
-    return TOMO_OK;
+    return reduce_tail([&] { hipLaunchKernelGGL(k_sum_rows_ascending, dim3((e->np * SN_SUMS + 255) / 256), dim3(256), 0, e->stream,
+                                                (const double *)e->al_part, e->al_out, e->np, nblk, SN_SUMS, (float *)nullptr, 0.0); },
+                       e, e->al_out, out_host, (size_t)e->np * SN_SUMS * sizeof(double));       // its wait also covers the matrices, read from the caller's host memory
 }
 
 int tomo_sino_axis_profile(tomo_engine *e, int sino, double *out_host)
@@ -183,10 +215,7 @@ int tomo_sino_axis_profile(tomo_engine *e, int sino, double *out_host)
     if ((rc = al_ensure(e, (void **)&e->al_out, &e->al_out_bytes, (size_t)e->np * e->nx * sizeof(double)))) return rc;
     hipLaunchKernelGGL(k_sino_axis_profile, dim3(nchunk, nblk, e->np), dim3(256), 0, e->stream, (const float *)g, e->al_part, e->n, e->nx, e->sx);
     LAUNCHCHK();
-    hipLaunchKernelGGL(k_sino_axis_profile_finish, dim3((e->np * e->nx + 255) / 256), dim3(256), 0, e->stream, (const double *)e->al_part,
-                       e->al_out, e->np, nblk, e->nx);
-    LAUNCHCHK();
-    HIPCHK(hipMemcpyAsync(out_host, e->al_out, (size_t)e->np * e->nx * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return TOMO_OK;
+    return reduce_tail([&] { hipLaunchKernelGGL(k_sum_rows_ascending, dim3((e->np * e->nx + 255) / 256), dim3(256), 0, e->stream,
+                                                (const double *)e->al_part, e->al_out, e->np, nblk, e->nx, (float *)nullptr, 0.0); },
+                       e, e->al_out, out_host, (size_t)e->np * e->nx * sizeof(double));
 }

@@ -146,11 +146,8 @@ int tomo_dart_class_stats(tomo_engine *e, int vol, const float *thr_host, int nt
     else if (nc <= 8) hipLaunchKernelGGL((k_dart_class_stats<8>), grid, block, 0, e->stream, (const float *)x, thr, nthr, nvec, e->nx, e->sx, e->dart_part);
     else hipLaunchKernelGGL((k_dart_class_stats<16>), grid, block, 0, e->stream, (const float *)x, thr, nthr, nvec, e->nx, e->sx, e->dart_part);
     LAUNCHCHK();
-    hipLaunchKernelGGL(k_dart_class_stats_finish, dim3(2 * nc), dim3(256), 0, e->stream, (const double *)e->dart_part, out, nblk);
-    LAUNCHCHK();
-    HIPCHK(hipMemcpyAsync(out_host, out, (size_t)2 * nc * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return TOMO_OK;
+    return reduce_tail([&] { hipLaunchKernelGGL(k_sum_rows_tree, dim3(2 * nc), dim3(256), 0, e->stream, (const double *)e->dart_part, out, nblk, 32); },
+                       e, out, out_host, (size_t)2 * nc * sizeof(double));
 }
 
 int tomo_dart_get_state(tomo_engine *e, uint8_t *out_host)

@@ -2,26 +2,20 @@
 // (tomo_volume_cross, tomo_volume_cross_axpy).
 // Part of tomo_engine.hip (included inside its extern "C" block, after engine_bin.inc); kernel: kernels_dual.hip.h.
 //
-// Two whole-volume engines on one device, both cubes of the same N (the NEED_ALIGN rule for both, and neither may be a slab of a
-// larger volume: crossing a slab is an all-to-all between the ranks).  Refusal, slot bookkeeping and ordering are those of
-// engine_bin.inc: everything that can be refused is refused before anything is enqueued or any engine state is touched; the kernel
-// runs on the destination engine's stream behind an event of the source's, and the source's stream then waits for the kernel.
+// Two whole-volume engines on one device, both cubes of the same N; neither may be a slab of a larger volume: crossing a slab is an
+// all-to-all between the ranks.  Refusal, slot bookkeeping and ordering: the pair rules of engine_bin.inc.
 
 static int cross_pair(tomo_engine *src, tomo_engine *dst, int src_vol, int dst_vol)
 {
-    if (!src || !dst) return fail(TOMO_ERR_ARG, "null engine");
+    const Pair p{src, dst, src_vol, dst_vol, false, "crossing the tilt axes"};
+    if (int rc = pair_check(p, PAIR_ENGINES)) return rc;
     if (src == dst) return fail(TOMO_ERR_ARG, "the source and the destination engine must be two engines");
-    if (src_vol < 0 || src_vol >= TOMO_VOL_SLOTS || dst_vol < 0 || dst_vol >= TOMO_VOL_SLOTS) return fail(TOMO_ERR_ARG, "bad volume id");
-    if (src->device != dst->device) return fail(TOMO_ERR_ARG, "the engines live on different devices");
+    if (int rc = pair_check(p, PAIR_SLOTS | PAIR_DEVICE)) return rc;
     if (src->nx != src->n || dst->nx != dst->n)
         return fail(TOMO_ERR_ARG, "both engines must hold a cube (Nslice == Nray): " + std::to_string(src->nx) + " x " + std::to_string(src->n) + "^2 and " +
                                       std::to_string(dst->nx) + " x " + std::to_string(dst->n) + "^2");
     if (src->n != dst->n) return fail(TOMO_ERR_ARG, "the engines differ in N (" + std::to_string(src->n) + " and " + std::to_string(dst->n) + ")");
-    NEED_ALIGN(src);
-    NEED_ALIGN(dst);
-    if (!(src->is_first && src->is_last) || !(dst->is_first && dst->is_last))
-        return fail(TOMO_ERR_STATE, "crossing the tilt axes needs whole volumes: an engine is a slab of a larger one (tomo_set_slab_edges)");
-    return TOMO_OK;
+    return pair_check(p, PAIR_STATE);
 }
 
 static int cross_launch(bool axpy, tomo_engine *src, int src_vol, tomo_engine *dst, int dst_vol, float a, int clamp)

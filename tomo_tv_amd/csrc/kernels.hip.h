@@ -18,6 +18,7 @@
 #include "kernels_tv.hip.h"       // TV value / gradient / update
 #include "kernels_fgp.hip.h"      // FGP-TV
 #include "kernels_pdhg.hip.h"     // Chambolle-Pock: dual sinogram, fused dual / divergence / primal pass
+#include "kernels_geom.hip.h"     // shared by the families below: axis split, bilinear / trilinear value, two-stage sums
 #include "kernels_align.hip.h"    // tilt-series alignment: moments, windowed cross-correlation, resampling
 #include "kernels_align_normal.hip.h" // per-projection similarity matching: gather, gradient and the 4 x 4 normal equations in one pass
 #include "kernels_bin.hip.h"      // binning of sinograms and volumes by 2 or 4, trilinear prolongation

@@ -6,16 +6,12 @@
 // differ.  m = {m00 .. m03, m10 .. m13, m20 .. m23} in binary64 maps a DESTINATION voxel (s, y, z) to its SOURCE position
 //     s' = fma(m00, s, fma(m01, y, fma(m02, z, m03))),   y' = fma(m10, s, fma(m11, y, fma(m12, z, m13))),   z' likewise with m2*,
 // three fused multiply-adds per coordinate, evaluated per voxel (the two inner links depend on the destination row alone and are
-// formed once per lane item of four voxels: the same operations on the same operands, the same bits).  Each coordinate is split
-// into floor and fraction in binary64; only the fraction is rounded to binary32, and one that rounds to 1 is the next whole voxel.
-// Per axis the weights
-// are w0 = 1 - t and w1 = t (binary32); an axis whose fraction is zero keeps only its first tap with w0 = 1 exactly -- the other tap
-// is neither loaded nor multiplied.  The kept taps x[dy][dz][ds] are combined in ascending (dy, dz, ds) order, ds fastest:
-//     o = ((wy[0] * wz[0]) * ws[0]) * x[0][0][0];   then for every further kept tap   o = fmaf((wy[dy] * wz[dz]) * ws[ds], x, o)
-// and a voxel whose three fractions are all zero copies the bits of its one tap.  A tap outside the source is 0 (not loaded); a
-// coordinate outside (-1, size) has no tap inside and gives 0 without a conversion to int (a NaN from Inf - Inf of huge finite
-// entries lands there too).  Hence an identity, a permutation of the axes, a whole-voxel translation, quarter turns and flips copy
-// samples bit for bit, and an Inf next to a copied sample stays out of the sum.
+// formed once per lane item of four voxels: the same operations on the same operands, the same bits).  Each coordinate is split by
+// axis_split<SPLIT_ZERO_PAD> into first tap, weights and the "second tap kept" flag, and the value is trilinear_value of the kept
+// taps (both kernels_geom.hip.h): an axis whose fraction is zero keeps only its first tap -- the other is neither loaded nor
+// multiplied.  A tap outside the source is 0 (not loaded); a coordinate outside (-1, size) has no tap inside and gives 0 (a NaN from
+// Inf - Inf of huge finite entries lands there too).  Hence an identity, a permutation of the axes, a whole-voxel translation,
+// quarter turns and flips copy samples bit for bit, and an Inf next to a copied sample stays out of the sum.
 //
 // Shape.  Lanes run along the destination's s, four consecutive slices per lane, one 16-byte store per lane: a 16-lane group writes
 // 256 contiguous bytes of a destination row, over the whole pitch (the slices Nslice .. sx-1 are stored as zero by this same
@@ -34,20 +30,6 @@ constexpr int AF_ROWS = 8;       // destination rows per workgroup
 
 struct Affine3 { double m[12]; };
 
-// one axis: coordinate c -> first tap i, weights w[2], and whether the second tap is kept; false: no tap inside [0, size)
-__device__ __forceinline__ bool af_split(double c, int size, int &i, float w[2], bool &two)
-{
-    if (!(c > -1.0 && c < (double)size)) return false;
-    const double f = floor(c);
-    float t = (float)(c - f);
-    i = (int)f;
-    if (t >= 1.f) { t = 0.f; ++i; }
-    two = t != 0.f;
-    w[0] = two ? 1.f - t : 1.f;
-    w[1] = t;
-    return true;
-}
-
 // the interpolated source value at destination voxel (s, row): by, bz, bs are the row's inner links of the three chains
 __device__ __forceinline__ float af_sample(const float *__restrict__ src, const Affine3 &M, double bs, double by, double bz, int s,
                                            int nxs, int ns, int sxs)
@@ -56,23 +38,15 @@ __device__ __forceinline__ float af_sample(const float *__restrict__ src, const 
     int is, iy, iz;
     float ws[2], wy[2], wz[2];
     bool ks, ky, kz;
-    if (!af_split(fma(M.m[0], sd, bs), nxs, is, ws, ks) || !af_split(fma(M.m[4], sd, by), ns, iy, wy, ky) ||
-        !af_split(fma(M.m[8], sd, bz), ns, iz, wz, kz))
+    if (!axis_split<SPLIT_ZERO_PAD>(fma(M.m[0], sd, bs), nxs, is, ws, ks) || !axis_split<SPLIT_ZERO_PAD>(fma(M.m[4], sd, by), ns, iy, wy, ky) ||
+        !axis_split<SPLIT_ZERO_PAD>(fma(M.m[8], sd, bz), ns, iz, wz, kz))
         return 0.f;
     auto tap = [&](int dy, int dz, int ds) -> float {
         const int y = iy + dy, z = iz + dz, q = is + ds;
         if ((unsigned)y >= (unsigned)ns || (unsigned)z >= (unsigned)ns || (unsigned)q >= (unsigned)nxs) return 0.f;
         return src[((size_t)y * ns + z) * (size_t)sxs + q];
     };
-    if (!ks && !ky && !kz) return tap(0, 0, 0);                     // a copy of bits
-    float o = __fmul_rn(__fmul_rn(__fmul_rn(wy[0], wz[0]), ws[0]), tap(0, 0, 0));
-#pragma unroll
-    for (int k = 1; k < 8; ++k) {
-        const int dy = k >> 2, dz = (k >> 1) & 1, ds = k & 1;
-        if ((dy && !ky) || (dz && !kz) || (ds && !ks)) continue;
-        o = __fmaf_rn(__fmul_rn(__fmul_rn(wy[dy], wz[dz]), ws[ds]), tap(dy, dz, ds), o);
-    }
-    return o;
+    return trilinear_value(tap, wy, wz, ws, ky, kz, ks);
 }
 
 // AXPY = false: dst = value (dst is not read).  AXPY = true: dst = fmaf(a, value, dst), then fmaxf(., 0) when clamp -- fmaxf returns

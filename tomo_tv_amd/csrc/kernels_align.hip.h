@@ -4,8 +4,7 @@
 //
 // Projection a of a sinogram is the image X_a[r][s], ray r in [0, N), slice s in [0, Nslice): device row a * N + r, slice fastest,
 // pitch sx.  The slices Nslice .. sx-1 are padding and are zero; every kernel here leaves them zero and none reads them as data.
-// No kernel of this family adds floats atomically: partial sums go to their own place and are added in index order in binary64,
-// so the results are the same bits from run to run.
+// The sums are two-stage sums in a fixed order (kernels_geom.hip.h): the same bits from run to run.
 #pragma once
 
 namespace tomo {
@@ -13,44 +12,23 @@ namespace tomo {
 // ---- per-angle moments: sum X, sum r X, sum s X over the real samples (cpu/utils/logger.py:237-247) ----------------------------
 // Workgroup (blk, a) takes AL_MROWS rays of projection a.  A thread keeps one slice column (per = 64, 128 or 256 threads side by side
 // on a row, the 256 / per row phases take alternate rows) and adds in binary64 from the first sample on: x, r * x and s * x are exact
-// there, so the only roundings are binary64 additions.  Wave sums by shuffle, the four waves in wave order, one triple per workgroup.
+// there, so the only roundings are binary64 additions.  One triple per workgroup (block_sum_row); k_sum_rows_ascending adds the
+// workgroups' triples and forms the means.
 constexpr int AL_MROWS = 32;
 
 __global__ __launch_bounds__(256) void k_sino_moments(const float *__restrict__ g, double *__restrict__ part, int n, int nx, int sx)
 {
-    __shared__ double red[4][3];
     const int a = blockIdx.y, blk = blockIdx.x;
     const int per = sx >= 256 ? 256 : (sx >= 128 ? 128 : 64), phase = threadIdx.x / per, nphase = 256 / per, col = threadIdx.x % per;
     const int r0 = blk * AL_MROWS, r1 = min(n, r0 + AL_MROWS);
     const float *base = g + (size_t)a * n * sx;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    double acc[3] = {0.0, 0.0, 0.0};
     for (int r = r0 + phase; r < r1; r += nphase)
         for (int s = col; s < nx; s += per) {
             const double x = (double)base[(size_t)r * sx + s];
-            s0 += x; s1 += (double)r * x; s2 += (double)s * x;
+            acc[0] += x; acc[1] += (double)r * x; acc[2] += (double)s * x;
         }
-    s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[w][0] = s0; red[w][1] = s1; red[w][2] = s2; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int k = threadIdx.x;
-        part[((size_t)a * gridDim.x + blk) * 3 + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-    }
-}
-
-// out[a][k] = the workgroups' triples added in ascending order; mean[a] = sum X / (N * Nslice) rounded to binary32 (what the
-// correlation subtracts while staging)
-__global__ void k_sino_moments_finish(const double *__restrict__ part, double *__restrict__ out, float *__restrict__ mean,
-                                      int np, int nblk, double count)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= np * 3) return;
-    const int a = i / 3, k = i - 3 * a;
-    double s = 0.0;
-    for (int b = 0; b < nblk; ++b) s += part[((size_t)a * nblk + b) * 3 + k];
-    out[i] = s;
-    if (k == 0) mean[a] = (float)(s / count);
+    block_sum_row<3>(acc, part + ((size_t)a * gridDim.x + blk) * 3);
 }
 
 // ---- windowed cross-correlation ------------------------------------------------------------------------------------------------
@@ -167,9 +145,8 @@ __global__ void k_sino_xcorr_finish(const double *__restrict__ part, double *__r
 // ---- resampling by per-angle shifts (cpu/utils/logger.py:249-250 with WRAP and whole-pixel shifts) ------------------------------
 // dst_a[r][s] = bilinear(src_a)(r - dr_a, s - ds_a).  The host splits -d into floor and fraction: tab[a] = {kr, ks, bits of tr, bits
 // of ts}, so the four taps are rows r + kr, r + kr + 1 and slices s + ks, s + ks + 1 with weights (1 - tr, tr) x (1 - ts, ts).  A tap
-// outside the image is 0, or with WRAP the sample modulo the image size (the host gives kr in [0, N), ks in [0, Nslice) then).  A
-// zero fraction drops its second tap altogether, so a whole-pixel shift copies the source value -- no 1 * x + 0 * y, which would
-// turn an Inf next to x into NaN.  Padding slices of dst are written as zero.
+// outside the image is 0, or with WRAP the sample modulo the image size (the host gives kr in [0, N), ks in [0, Nslice) then).  The
+// value is bilinear_value (kernels_geom.hip.h): a whole-pixel shift copies the source value.  Padding slices of dst are written as zero.
 template <bool WRAP>
 __global__ __launch_bounds__(256) void k_sino_shift(const float *__restrict__ src, float *__restrict__ dst, const int4 *__restrict__ tab,
                                                     int n, int nx, int sx)
@@ -188,18 +165,7 @@ __global__ __launch_bounds__(256) void k_sino_shift(const float *__restrict__ sr
     const int total = n * sx;
     for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
         const int r = idx / sx, s = idx - r * sx;
-        float o = 0.f;
-        if (s < nx) {
-            const int i = r + kr, j = s + ks;
-            if (tr == 0.f && ts == 0.f) o = fetch(i, j);
-            else if (tr == 0.f) o = (1.f - ts) * fetch(i, j) + ts * fetch(i, j + 1);
-            else if (ts == 0.f) o = (1.f - tr) * fetch(i, j) + tr * fetch(i + 1, j);
-            else {
-                const float wr = 1.f - tr, ws = 1.f - ts;
-                o = (wr * ws) * fetch(i, j) + (wr * ts) * fetch(i, j + 1) + (tr * ws) * fetch(i + 1, j) + (tr * ts) * fetch(i + 1, j + 1);
-            }
-        }
-        D[idx] = o;
+        D[idx] = s < nx ? bilinear_value(fetch, r + kr, s + ks, tr, ts) : 0.f;
     }
 }
 
@@ -208,13 +174,12 @@ __global__ __launch_bounds__(256) void k_sino_shift(const float *__restrict__ sr
 // m12} in binary64.  The layout and the grid are k_sino_shift's: lane = slice, s fastest, one 4-byte write per element, coalesced;
 // the reads of a wave are the source row(s) its destination row maps to -- for the few degrees of a tilt-axis correction a wave's 64
 // slices touch a handful of neighbouring source rows, 256-byte runs that the L2 serves.  The coordinates are binary64, evaluated
-// per element as fma(m00, r, fma(m01, s, m02)) and split into floor and fraction in binary64; only the fraction is rounded to
-// binary32 (a fraction that rounds to 1 is the next whole pixel, as in al_split).  Four binary64 FMAs, two floors and two conversions
-// per element beside one read and one write: at half the binary32 rate still an order below the time the bytes take.  Weights and
-// the four-tap expression are k_sino_shift's, operation for operation: a zero fraction drops its tap, so an identity copies the
-// source bits, a pure translation gives tomo_sino_shift's bits (wrap = 0) and an Inf next to a copied sample stays out of the
-// sum.  A tap outside [0, n) x [0, nx) is 0; a coordinate outside (-1, n) x (-1, nx) has no tap inside -- it gives 0 without a
-// conversion to int (a NaN from Inf - Inf of huge finite entries lands here too).  Padding slices of dst are written as zero.
+// per element as fma(m00, r, fma(m01, s, m02)) and split by axis_split<SPLIT_ZERO_PAD> (kernels_geom.hip.h).  Four binary64 FMAs,
+// two floors and two conversions per element beside one read and one write: at half the binary32 rate still an order below the time
+// the bytes take.  The value is the bilinear_value that k_sino_shift evaluates: an identity copies the source bits, a pure
+// translation gives tomo_sino_shift's bits (wrap = 0) and an Inf next to a copied sample stays out of the sum.  A tap outside
+// [0, n) x [0, nx) is 0; a coordinate outside (-1, n) x (-1, nx) has no tap inside and gives 0 (a NaN from Inf - Inf of huge finite
+// entries lands here too).  Padding slices of dst are written as zero.
 __global__ __launch_bounds__(256) void k_sino_affine(const float *__restrict__ src, float *__restrict__ dst, const double *__restrict__ mat,
                                                      int n, int nx, int sx)
 {
@@ -234,20 +199,9 @@ __global__ __launch_bounds__(256) void k_sino_affine(const float *__restrict__ s
         if (s < nx) {
             const double rp = fma(m00, (double)r, fma(m01, (double)s, m02));
             const double sp = fma(m10, (double)r, fma(m11, (double)s, m12));
-            if (rp > -1.0 && rp < (double)n && sp > -1.0 && sp < (double)nx) {
-                const double fr = floor(rp), fs = floor(sp);
-                float tr = (float)(rp - fr), ts = (float)(sp - fs);
-                int i = (int)fr, j = (int)fs;
-                if (tr >= 1.f) { tr = 0.f; ++i; }
-                if (ts >= 1.f) { ts = 0.f; ++j; }
-                if (tr == 0.f && ts == 0.f) o = fetch(i, j);
-                else if (tr == 0.f) o = (1.f - ts) * fetch(i, j) + ts * fetch(i, j + 1);
-                else if (ts == 0.f) o = (1.f - tr) * fetch(i, j) + tr * fetch(i + 1, j);
-                else {
-                    const float wr = 1.f - tr, ws = 1.f - ts;
-                    o = (wr * ws) * fetch(i, j) + (wr * ts) * fetch(i, j + 1) + (tr * ws) * fetch(i + 1, j) + (tr * ts) * fetch(i + 1, j + 1);
-                }
-            }
+            int i, j;
+            float tr, ts;
+            if (axis_split<SPLIT_ZERO_PAD>(rp, n, i, tr) && axis_split<SPLIT_ZERO_PAD>(sp, nx, j, ts)) o = bilinear_value(fetch, i, j, tr, ts);
         }
         D[idx] = o;
     }
@@ -256,8 +210,8 @@ __global__ __launch_bounds__(256) void k_sino_affine(const float *__restrict__ s
 // ---- per-slice mass profile: c_a[s] = sum_r X_a[r][s] (the common line of a parallel-beam series: the same for every tilt) --------
 // Workgroup (ch, blk, a) takes the 64 slices [64 ch, 64 ch + 64) of AL_PROWS rays of projection a.  Lane = slice: wave w adds rows
 // r0 + w, r0 + w + 4, ... in ascending order, in binary64 from the first sample (a row read of a wave is 256 consecutive bytes); the
-// four waves' sums are added in wave order, one value per (angle, workgroup, slice), and k_sino_axis_profile_finish adds the
-// workgroups' in ascending order.
+// four waves' sums are added in wave order, one value per (angle, workgroup, slice) -- lane-wise, with no sum across lanes, so this
+// is not block_sum_row -- and k_sum_rows_ascending adds the workgroups' rows.
 constexpr int AL_PROWS = 64;
 
 __global__ __launch_bounds__(256) void k_sino_axis_profile(const float *__restrict__ g, double *__restrict__ part, int n, int nx, int sx)
@@ -273,17 +227,6 @@ __global__ __launch_bounds__(256) void k_sino_axis_profile(const float *__restri
     red[w][lane] = acc;
     __syncthreads();
     if (w == 0 && s < nx) part[((size_t)a * gridDim.y + blk) * nx + s] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
-}
-
-// out[a][s] = the workgroups' sums added in ascending order
-__global__ void k_sino_axis_profile_finish(const double *__restrict__ part, double *__restrict__ out, int np, int nblk, int nx)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= np * nx) return;
-    const int a = i / nx, s = i - a * nx;
-    double acc = 0.0;
-    for (int b = 0; b < nblk; ++b) acc += part[((size_t)a * nblk + b) * nx + s];
-    out[i] = acc;
 }
 
 }  // namespace tomo

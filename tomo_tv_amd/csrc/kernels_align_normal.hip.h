@@ -5,19 +5,20 @@
 // F_a is projection a of the fixed sinogram (the model; the destination grid of tomo_sino_affine), G_a projection a of the moving one
 // (the series as given; the source), both X_a[r][s] with the engine's sizes and pitch.  mat[a] = {m00, m01, m02, m10, m11, m12} maps a
 // sample (r, s) of F_a to its position p = (r', s') in G_a: the chain of k_sino_affine, r' = fma(m00, r, fma(m01, s, m02)),
-// s' = fma(m10, r, fma(m11, s, m12)) in binary64; each coordinate is split into floor and fraction in binary64, only the fraction t is
-// rounded to binary32, and one that rounds to 1 is the next whole pixel with t = 0.
+// s' = fma(m10, r, fma(m11, s, m12)) in binary64; each coordinate is split by axis_split<SPLIT_INSIDE> (kernels_geom.hip.h).
 //
 // Which samples count.  Both must hold: (a) all four tap positions lie inside G_a, 0 <= i and i + 1 <= size - 1 on both axes with i the
-// first tap AFTER the split (so a coordinate just below 0 whose fraction rounds to 1 is pixel 0 and can count; stricter than the zero padding of k_sino_affine: a sample on the last row of G does not count even with
-// t = 0); (b) margin <= r <= Nray - 1 - margin and margin <= s <= Nslice - 1 - margin.  A sample that does not count loads no tap and
+// first tap AFTER the split (so a coordinate just below 0 whose fraction rounds to 1 is pixel 0 and can count; stricter than the zero
+// padding of k_sino_affine: a sample on the last row of G does not count even with t = 0); (b) margin <= r <= Nray - 1 - margin and margin <= s <= Nslice - 1 - margin.  A sample that does not count loads no tap and
 // adds nothing (a branch, never a product with 0): an Inf or a NaN there, or in a sample of G that is no tap of a counting sample,
 // stays out.  A counting sample loads all four taps x[di][dj] (di along r, dj along s), whatever its fractions.  Padding slices
 // (s >= Nslice) are never read as data: they fail (b) as samples and (a) as taps.
 //
 // Per counting sample, in binary32 with every operation rounded once:
-//   value     w   = the four-tap expression of k_sino_affine as it is written there, every product and every sum an operation of
-//                 its own (no fused multiply-add: the intrinsics below say so; tests/ref64_affine.py replays the same operations):
+//   value     w   = the formula of bilinear_value, here with every product and every sum an operation of its own (no fused
+//                 multiply-add: the intrinsics below say so; tests/ref64_affine.py replays the same operations).  The taps are needed
+//                 for the gradient anyway.  This is the UNCONTRACTED evaluation: k_sino_affine's compiled bilinear_value is
+//                 contracted into fused multiply-adds, so w is not bit-equal to what tomo_sino_affine writes for the same map:
 //                   tr = ts = 0:  x00
 //                   tr = 0:       (1 - ts) x00 + ts x01
 //                   ts = 0:       (1 - tr) x00 + tr x10
@@ -39,26 +40,14 @@
 // Shape.  Lane = slice: workgroup (blk, a) takes the SN_ROWS rays [SN_ROWS blk, SN_ROWS (blk + 1)) of projection a, a thread the items
 // idx = threadIdx.x, threadIdx.x + 256, ... of them (row idx / sx, slice idx % sx: a wave reads 64 consecutive slices of one row of F,
 // 256 bytes, and gathers G through the cache hierarchy with 4-byte loads) and adds its samples in that order into 21 binary64 registers.
-// The workgroup adds its threads by the wave tree (wave_sum), then its four waves in ascending order, and writes part[a][blk][21];
-// k_sino_affine_normal_finish adds the workgroups of a projection in ascending order.  No atomics, no LDS but the 4 x 21 wave sums:
-// the same bits from call to call.  Nothing but part and out is written.
+// The workgroup's 21 sums go to part[a][blk][21] (block_sum_row) and k_sum_rows_ascending adds the workgroups of a projection.  No
+// atomics, no LDS but the 4 x 21 wave sums: the same bits from call to call.  Nothing but part and out is written.
 #pragma once
 
 namespace tomo {
 
 constexpr int SN_ROWS = 16;          // rays per workgroup of k_sino_affine_normal
 constexpr int SN_SUMS = 21;
-
-// one axis for the strict rule: coordinate c -> first tap i with both taps i, i + 1 inside [0, size), fraction t; false otherwise
-__device__ __forceinline__ bool sn_split(double c, int size, int &i, float &t)
-{
-    if (!(c > -1.0 && c < (double)size)) return false;         // k_sino_affine's range: keeps the conversion to int in range (a NaN lands here)
-    const double f = floor(c);
-    t = (float)(c - f);
-    i = (int)f;
-    if (t >= 1.f) { t = 0.f; ++i; }                            // c in [-2^-25, 0) is pixel 0 with t = 0, as the split says
-    return i >= 0 && i + 1 <= size - 1;
-}
 
 // grid = (ceil(n / SN_ROWS), np); 256 threads
 __global__ __launch_bounds__(256) void k_sino_affine_normal(const float *__restrict__ F, const float *__restrict__ G,
@@ -81,7 +70,7 @@ __global__ __launch_bounds__(256) void k_sino_affine_normal(const float *__restr
         const double sp = fma(m10, (double)r, fma(m11, (double)s, m12));
         int i, j;
         float tr, ts;
-        if (!sn_split(rp, n, i, tr) || !sn_split(sp, nx, j, ts)) continue;
+        if (!axis_split<SPLIT_INSIDE>(rp, n, i, tr) || !axis_split<SPLIT_INSIDE>(sp, nx, j, ts)) continue;
         // the four taps: all inside G_a by the rule above
         const float *g0 = Ga + (size_t)i * sx + j;
         const float x00 = g0[0], x01 = g0[1], x10 = g0[sx], x11 = g0[sx + 1];
@@ -118,29 +107,7 @@ __global__ __launch_bounds__(256) void k_sino_affine_normal(const float *__restr
         acc[19] += fd;
         acc[20] += wd;
     }
-    __shared__ double red[4][SN_SUMS];
-    const int wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < SN_SUMS; ++k) {
-        const double v = wave_sum(acc[k]);
-        if ((threadIdx.x & 63) == 0) red[wv][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < SN_SUMS) {
-        const int k = threadIdx.x;
-        part[((size_t)a * gridDim.x + blk) * SN_SUMS + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-    }
-}
-
-// out[a][k] = the workgroups' sums part[a][b][k], b < nblk, added in ascending order; one thread per (a, k)
-__global__ void k_sino_affine_normal_finish(const double *__restrict__ part, double *__restrict__ out, int np, int nblk)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= np * SN_SUMS) return;
-    const int a = i / SN_SUMS, k = i - SN_SUMS * a;
-    double s = 0.0;
-    for (int b = 0; b < nblk; ++b) s += part[((size_t)a * nblk + b) * SN_SUMS + k];
-    out[i] = s;
+    block_sum_row<SN_SUMS>(acc, part + ((size_t)a * gridDim.x + blk) * SN_SUMS);
 }
 
 }  // namespace tomo

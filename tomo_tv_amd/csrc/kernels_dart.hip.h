@@ -291,18 +291,17 @@ __global__ __launch_bounds__(256) void k_dart_smooth(const float *__restrict__ x
 // out[c] = {sum of x, count} over the real voxels of class c (the label rule of k_dart_classify), in binary64.  A voxel that is not
 // finite is counted in its class (NaN: class 0; +Inf: the last; -Inf: class 0) but NOT summed: one such voxel would otherwise
 // make the mean of its class useless.
-// Two stages in a fixed order: a thread adds the voxels it strides over in ascending order, a workgroup adds its threads by the
-// wave tree and then its four waves, and writes part[block][c][2]; k_dart_class_stats_finish adds the workgroups' rows: thread t of
-// the output's workgroup takes the rows t, t + 256, ... in ascending order, then the same tree.
+// Two stages in a fixed order (kernels_geom.hip.h): a thread adds the voxels it strides over in ascending order into acc[c][2] =
+// {sum, count}, the workgroup's sums go to part[block][c][2] (block_sum_row) and k_sum_rows_tree adds the workgroups' rows.
 constexpr int DART_STATS_BLOCKS = 1024;
 
 template <int NC>
 __global__ __launch_bounds__(256) void k_dart_class_stats(const float *__restrict__ x, DartThr thr, int nthr, int64_t nvec, int nx, int sx,
                                                           double *__restrict__ part)
 {
-    double sum[NC], cnt[NC];
+    double acc[2 * NC];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) sum[c] = cnt[c] = 0.0;
+    for (int k = 0; k < 2 * NC; ++k) acc[k] = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
         const int s = (int)((i * 4) % sx);
         const VecOf<4>::T q = reinterpret_cast<const VecOf<4>::T *>(x)[i];
@@ -316,36 +315,12 @@ __global__ __launch_bounds__(256) void k_dart_class_stats(const float *__restric
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
                 const bool in = real && lab[k] == c;
-                sum[c] += in ? a : 0.0;
-                cnt[c] += in ? 1.0 : 0.0;
+                acc[2 * c] += in ? a : 0.0;
+                acc[2 * c + 1] += in ? 1.0 : 0.0;
             }
         }
     }
-    __shared__ double red[4][NC][2];
-    const int w = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const double a = wave_sum(sum[c]), b = wave_sum(cnt[c]);
-        if ((threadIdx.x & 63) == 0) { red[w][c][0] = a; red[w][c][1] = b; }
-    }
-    __syncthreads();
-    if (threadIdx.x < NC * 2) {
-        const int c = threadIdx.x >> 1, f = threadIdx.x & 1;
-        part[((size_t)blockIdx.x * 16 + c) * 2 + f] = ((red[0][c][f] + red[1][c][f]) + red[2][c][f]) + red[3][c][f];
-    }
-}
-
-// out[o] = the sum of part[b][o], b < nblk (o = class * 2 + field; one workgroup per output)
-__global__ __launch_bounds__(256) void k_dart_class_stats_finish(const double *__restrict__ part, double *__restrict__ out, int nblk)
-{
-    const int o = blockIdx.x;
-    double v = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += 256) v += part[(size_t)b * 32 + o];
-    __shared__ double red[4];
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) out[o] = ((red[0] + red[1]) + red[2]) + red[3];
+    block_sum_row<2 * NC>(acc, part + (size_t)blockIdx.x * 32);
 }
 
 // ---- k_dart_state_out: the state buffer [pix][sx] as the host's [Nslice][Ny][Nz] bytes ------------------------------------------

@@ -5,20 +5,19 @@
 // F is the fixed volume (the destination grid of tomo_volume_affine), G the moving one (the source); both [pixel = y N + z][slice s]
 // with their own sizes and pitches.  A voxel x = (s, y, z) of F has the position p = M x in G: the coordinate chain of
 // k_volume_affine, three fused multiply-adds per coordinate in binary64, the two inner links once per item of four voxels; each
-// coordinate is split into floor and fraction in binary64, only the fraction t is rounded to binary32, and one that rounds to 1 is
-// the next whole voxel with t = 0.
+// coordinate is split by axis_split<SPLIT_INSIDE_FROM_ZERO> (kernels_geom.hip.h).
 //
-// Which voxels count.  Both must hold: (a) all eight tap positions lie inside G, 0 <= i and i + 1 <= size - 1 on every axis with i the
-// first tap after the split (stricter than the zero padding of k_volume_affine: a voxel on the last plane of G does not count even
-// with t = 0); (b) margin <= x <= size - 1 - margin on every axis of F.  A voxel that does not count loads no tap and adds nothing
+// Which voxels count.  Both must hold: (a) all eight tap positions lie inside G: 0 <= c on every axis, judged on the coordinate
+// itself BEFORE the split (0 <= floor(c), as tests/ref64_register3d.py states it: a c in [-2^-25, 0) does not count although its
+// split would be voxel 0 with t = 0 -- k_sino_affine_normal's rule takes such a sample), and i + 1 <= size - 1 with i the first tap
+// after the split (stricter than the zero padding of k_volume_affine: a voxel on the last plane of G does not count even with
+// t = 0); (b) margin <= x <= size - 1 - margin on every axis of F.  A voxel that does not count loads no tap and adds nothing
 // (a branch, never a product with 0): an Inf or a NaN there, or in a voxel of G that is no tap of a counting voxel, stays out.  A
 // counting voxel loads all eight taps x[dy][dz][ds], whatever its fractions.
 //
 // Per counting voxel, in binary32 with every operation rounded once (weights per axis w[0] = 1 - t, w[1] = t, and w[0] = 1 exactly
-// where t = 0, as af_split gives them):
-//   value     w   = the expression of af_sample: the kept taps (an axis with t = 0 keeps its first tap only) in ascending
-//                   (dy, dz, ds) order, ds fastest; the first as ((wy wz) ws) x, every further one o = fmaf((wy wz) ws, x, o); three
-//                   zero fractions copy the tap's bits.
+// where t = 0, as axis_split gives them):
+//   value     w   = trilinear_value of the kept taps (an axis with t = 0 keeps its first tap only): the bits of k_volume_affine.
 //   gradient  g_s = (wy0 wz0) e00;  then fmaf(wy0 wz1, e01, .), fmaf(wy1 wz0, e10, .), fmaf(wy1 wz1, e11, .)
 //                   with e[dy][dz] = x[dy][dz][1] - x[dy][dz][0]
 //             g_y = (wz0 ws0) e00;  then fmaf(wz0 ws1, e01, .), fmaf(wz1 ws0, e10, .), fmaf(wz1 ws1, e11, .)
@@ -37,30 +36,15 @@
 //
 // Shape.  Lanes, items of four slices and AF_ROWS rows per block of rows as in k_volume_affine; F is read with one 16-byte load per
 // item, G through the cache hierarchy with 4-byte loads.  The grid is capped at RG_BLOCKS workgroups, workgroup b takes the blocks of
-// rows b, b + gridDim.x, ...: a thread adds its voxels in that order into 32 binary64 registers, the workgroup adds its threads by the
-// wave tree (wave_sum) and then its four waves in ascending order and writes part[b][32]; k_affine_normal_finish adds the
-// workgroups' rows: thread t of output o takes the rows t, t + 256, ... in ascending order, then the same tree.  No atomics: the same
-// bits from call to call.  Nothing but part and out is written.
+// rows b, b + gridDim.x, ...: a thread adds its voxels in that order into 32 binary64 registers, the workgroup's sums go to part[b][32]
+// (block_sum_row) and k_sum_rows_tree adds the workgroups' rows.  No atomics: the same bits from call to call.  Nothing but part and
+// out is written.
 #pragma once
 
 namespace tomo {
 
 constexpr int RG_BLOCKS = 1024;      // the most workgroups of k_volume_affine_normal: bounds part[RG_BLOCKS + 1][32] (the last row: the result)
 constexpr int RG_SUMS = 32;
-
-// one axis for the strict rule: coordinate c -> first tap i with both taps i, i + 1 inside [0, size), weights w[2]; false otherwise
-__device__ __forceinline__ bool rg_split(double c, int size, int &i, float w[2], bool &two)
-{
-    if (!(c >= 0.0 && c < (double)size)) return false;         // also keeps the conversion to int in range (a NaN lands here)
-    const double f = floor(c);
-    float t = (float)(c - f);
-    i = (int)f;
-    if (t >= 1.f) { t = 0.f; ++i; }
-    two = t != 0.f;
-    w[0] = two ? 1.f - t : 1.f;
-    w[1] = t;
-    return i + 1 <= size - 1;
-}
 
 // grid.x = min(RG_BLOCKS, ceil(N_F^2 / AF_ROWS)); 256 threads
 __global__ __launch_bounds__(256) void k_volume_affine_normal(const float *__restrict__ F, const float *__restrict__ G, Affine3 M, int nxs,
@@ -94,22 +78,14 @@ __global__ __launch_bounds__(256) void k_volume_affine_normal(const float *__res
                 int is, iy, iz;
                 float ws[2], wy[2], wz[2];
                 bool ks, ky, kz;
-                if (!rg_split(ps, nxs, is, ws, ks) || !rg_split(py, ns, iy, wy, ky) || !rg_split(pz, ns, iz, wz, kz)) continue;
+                if (!axis_split<SPLIT_INSIDE_FROM_ZERO>(ps, nxs, is, ws, ks) || !axis_split<SPLIT_INSIDE_FROM_ZERO>(py, ns, iy, wy, ky) ||
+                    !axis_split<SPLIT_INSIDE_FROM_ZERO>(pz, ns, iz, wz, kz))
+                    continue;
                 // the eight taps x[dy][dz][ds] at index dy 4 + dz 2 + ds: all inside G by the rule above
                 const float *g0 = G + ((size_t)iy * ns + iz) * (size_t)sxs + is;
                 const size_t oz = (size_t)sxs, oy = (size_t)ns * sxs;
                 const float x[8] = {g0[0], g0[1], g0[oz], g0[oz + 1], g0[oy], g0[oy + 1], g0[oy + oz], g0[oy + oz + 1]};
-                float w;
-                if (!ks && !ky && !kz) w = x[0];
-                else {
-                    w = __fmul_rn(__fmul_rn(__fmul_rn(wy[0], wz[0]), ws[0]), x[0]);
-#pragma unroll
-                    for (int j = 1; j < 8; ++j) {
-                        const int dy = j >> 2, dz = (j >> 1) & 1, ds = j & 1;
-                        if ((dy && !ky) || (dz && !kz) || (ds && !ks)) continue;
-                        w = __fmaf_rn(__fmul_rn(__fmul_rn(wy[dy], wz[dz]), ws[ds]), x[j], w);
-                    }
-                }
+                const float w = trilinear_value([&](int dy, int dz, int ds) { return x[dy * 4 + dz * 2 + ds]; }, wy, wz, ws, ky, kz, ks);
                 float gs = __fmul_rn(__fmul_rn(wy[0], wz[0]), __fsub_rn(x[1], x[0]));
                 gs = __fmaf_rn(__fmul_rn(wy[0], wz[1]), __fsub_rn(x[3], x[2]), gs);
                 gs = __fmaf_rn(__fmul_rn(wy[1], wz[0]), __fsub_rn(x[5], x[4]), gs);
@@ -144,31 +120,7 @@ __global__ __launch_bounds__(256) void k_volume_affine_normal(const float *__res
             }
         }
     }
-    __shared__ double red[4][RG_SUMS];
-    const int wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < RG_SUMS; ++k) {
-        const double a = wave_sum(acc[k]);
-        if ((threadIdx.x & 63) == 0) red[wv][k] = a;
-    }
-    __syncthreads();
-    if (threadIdx.x < RG_SUMS) {
-        const int k = threadIdx.x;
-        part[(size_t)blockIdx.x * RG_SUMS + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-    }
-}
-
-// out[o] = the sum of part[b][o], b < nblk; one workgroup of 256 threads per output, grid.x = RG_SUMS
-__global__ __launch_bounds__(256) void k_affine_normal_finish(const double *__restrict__ part, double *__restrict__ out, int nblk)
-{
-    const int o = blockIdx.x;
-    double v = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += 256) v += part[(size_t)b * RG_SUMS + o];
-    __shared__ double red[4];
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) out[o] = ((red[0] + red[1]) + red[2]) + red[3];
+    block_sum_row<RG_SUMS>(acc, part + (size_t)blockIdx.x * RG_SUMS);
 }
 
 }  // namespace tomo
