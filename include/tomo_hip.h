@@ -246,6 +246,28 @@ int tomo_sino_affine_normal(tomo_engine *e, int fixed_sino, int moving_sino, con
                             double *out_host /* [Nproj][21] */);                             /* waits */
 int tomo_sino_axis_profile(tomo_engine *e, int sino, double *out_host);                      /* [Nproj][Nslice] */
 
+/* ---- refinement of the per-projection tilt angles (kernels_tilt.hip.h; the drivers are align.match_tilt_angles and
+ * TomoGPU.refine_tilt_angles) ----------------------------------------------------------------------------------------------
+ * The reference takes the tilt angles as given (tomoengine.cpp:128-149 only replaces them); these two calls are what estimating them
+ * needs.  In the convention of the system matrix (cpu/utils/pytvlib.py:8-121: pixel i * N + j of a slice at X = j - (N - 1) / 2,
+ * Y = (N - 1) / 2 - i; ray t of angle theta through (t cos, t sin) along (-sin, cos)) the derivative of a projection by its own angle
+ * is the projection of ONE volume, d g_theta / d theta = A_theta (D f) with D f = X d_Y f - Y d_X f.  One whole-volume engine, like the
+ * alignment calls above: TOMO_ERR_STATE on an engine with a communicator, a slab of a larger volume (tomo_set_slab_edges) or released
+ * geometry.  A refused call enqueues nothing and writes nothing.
+ *   tomo_volume_rot_derivative: dst = D src per slice, central differences (f[+1] - f[-1]) / 2 across the pixel grid, taken as 0 in
+ *       the direction that crosses the border (rows 0 and N - 1 for d_Y, columns 0 and N - 1 for d_X).  Binary32, every operation
+ *       rounded once: dy = f[i - 1][j] - f[i + 1][j], dx = f[i][j + 1] - f[i][j - 1], q = (0.5 Y) dx, dst = fma(0.5 X, dy, -q); the
+ *       halved coordinates are exact.  A constant slice gives exact zeros; padding stays zero.  Enqueued on the engine's stream, no
+ *       wait.  TOMO_ERR_ARG: a bad slot, src_vol == dst_vol.
+ *   tomo_sino_tilt_normal: one pass over three sinogram slots, the data b, the model g and the derivative d.  out_host[a] =
+ *       {sum (b - g) d, sum d^2, sum (b - g)^2, the count} over the samples of projection a with margin <= ray <= Nray - 1 - margin and
+ *       margin <= slice <= Nslice - 1 - margin, in binary64 from the first sample (the products by fused multiply-add); a sample that
+ *       does not count is not looked at.  The Gauss-Newton step of angle a is out[a][0] / out[a][1] radians.  Two fixed-order
+ *       reduction stages, no atomics: the same bits from call to call.  The slots are only read (no claim on TOMO_SINO_G is dropped)
+ *       and may coincide.  Waits for its result.  TOMO_ERR_ARG: a bad slot, a null pointer, margin < 0 or 2 * margin >= Nray or Nslice. */
+int tomo_volume_rot_derivative(tomo_engine *e, int src_vol, int dst_vol);
+int tomo_sino_tilt_normal(tomo_engine *e, int b_sino, int g_sino, int d_sino, int margin, double *out_host /* [Nproj][4] */);  /* waits */
+
 /* ---- binning and prolongation between two engines (coarse-to-fine drivers) --------------------------------------------------
  * `fine` and `coarse` are two different whole-volume engines on one device whose grids differ by factor = f, 2 or 4:
  *     fine Nray == f * coarse Nray,   coarse Nslice == ceil(fine Nslice / f),   and for tomo_sino_bin the same Nproj.

@@ -5,8 +5,12 @@ The windows are ``Nangles * (2S+1)^2`` doubles, the matrices ``Nangles * 6`` and
 bookkeeping, not hot path: the correlation itself, the moments, the profiles and the resampling are HIP kernels
 (``tomoengine.sino_xcorr`` / ``sino_moments`` / ``sino_axis_profile`` / ``sino_shift`` / ``sino_affine``).  Likewise the Gauss-Newton
 loops of the 3-D registration and of the per-projection similarity matching: the normal equations are reduced on the device
-(``volume_affine_normal`` / ``sino_affine_normal``), the 6 x 6 and 4 x 4 solves and the composition of the maps happen here."""
+(``volume_affine_normal`` / ``sino_affine_normal``), the 6 x 6 and 4 x 4 solves and the composition of the maps happen here.  The
+tilt angles are refined the same way: ``volume_rot_derivative`` and ``sino_tilt_normal`` reduce four numbers per projection on the
+device, the division, the clip and the gauge are here (``tilt_increment``, ``match_tilt_angles``)."""
 import numpy as np
+
+from ._lib import SINO_G, SINO_USER0, VOL_RECON, VOL_TEMP
 
 
 def _parabola(cm, c0, cp):
@@ -361,6 +365,55 @@ def match_projections(eng, fixed, moving, M0=None, max_iter=20, tol_shift=1e-3, 
     out["M"] = M
     out["shift"], out["rotation_deg"], out["magnification"] = decode_similarity(M, N, ns)
     return out
+
+
+# ---- per-projection tilt angles: the host side of ``tomoengine.sino_tilt_normal`` (4 numbers per projection and evaluation) ---------
+TILT_SCRATCH_SLOT = SINO_USER0 + 37    # sinogram slot the derivative's projections go to, unless the caller names another
+
+
+def tilt_increment(rd, dd, damping=1.0, max_step_deg=None):
+    """The Gauss-Newton step of every tilt angle in DEGREES from the sums of ``sino_tilt_normal``: ``damping * rd / dd`` radians,
+    exactly 0 where ``dd == 0`` (a projection whose derivative vanishes says nothing about its angle), clipped to
+    +-``max_step_deg`` where that is given, and THEN with the mean removed: a common offset of all angles is a rotation of the
+    volume about the tilt axis, which the data cannot see, so the increments of a pass carry none.  (After the clip a step can
+    therefore exceed ``max_step_deg`` by the removed mean.)  ``damping`` is the fraction of the full step that is taken, 1.0 = all of
+    it.  ``ValueError`` for sums that are not finite, a negative ``dd``, a ``damping`` outside (0, 1] or a ``max_step_deg`` that is
+    not positive."""
+    rd, dd = np.asarray(rd, np.float64).ravel(), np.asarray(dd, np.float64).ravel()
+    if rd.shape != dd.shape or rd.size == 0:
+        raise ValueError("rd and dd must hold one value per projection")
+    if not (np.all(np.isfinite(rd)) and np.all(np.isfinite(dd))) or np.any(dd < 0.0):
+        raise ValueError("the sums must be finite and dd must not be negative")
+    if not 0.0 < float(damping) <= 1.0:
+        raise ValueError("damping must lie in (0, 1]")
+    if max_step_deg is not None and not float(max_step_deg) > 0.0:
+        raise ValueError("max_step_deg must be positive")
+    step = np.zeros_like(rd)
+    ok = dd > 0.0
+    step[ok] = np.rad2deg(float(damping) * rd[ok] / dd[ok])
+    if max_step_deg is not None:
+        step = np.clip(step, -float(max_step_deg), float(max_step_deg))
+    return step - step.mean()
+
+
+def match_tilt_angles(eng, b_sino, vol=VOL_RECON, margin=1, deriv_vol=VOL_TEMP, deriv_sino=TILT_SCRATCH_SLOT):
+    """One evaluation of the tilt-angle matching on engine ``eng``: how well the projections of volume ``vol`` at the engine's
+    angles explain the data in sinogram slot ``b_sino``, and in which direction every angle should move.  Four device steps: the
+    rotational derivative of ``vol`` (``volume_rot_derivative``), the projection of ``vol`` (the model) and of the derivative, and
+    the per-projection sums (``sino_tilt_normal``) over the samples ``margin`` inside the image.  -> ``(rd, dd, rr, count)``
+    (``tilt_increment(rd, dd)`` turns them into steps; ``rr`` is the squared data distance per projection over the same samples).
+
+    OVERWRITES: volume slot ``deriv_vol`` (default ``VOL_TEMP``, the slot of ``copy_recon``) with the derivative volume; sinogram slot
+    ``SINO_G`` with the model ``A vol`` (as ``forward_projection`` does); sinogram slot ``deriv_sino`` (default
+    ``TILT_SCRATCH_SLOT`` = ``SINO_USER0 + 37``) with ``A (D vol)``.  ``vol`` and ``b_sino`` are only read."""
+    if int(deriv_vol) == int(vol):
+        raise ValueError("deriv_vol must be another slot than vol")
+    if int(deriv_sino) in (int(b_sino), SINO_G):
+        raise ValueError("deriv_sino must be neither the data slot nor SINO_G")
+    eng.volume_rot_derivative(vol, deriv_vol)
+    eng.be.c("forward_projection", int(vol), SINO_G)
+    eng.be.c("forward_projection", int(deriv_vol), int(deriv_sino))
+    return eng.sino_tilt_normal(b_sino, SINO_G, deriv_sino, margin=margin)
 
 
 def axis_score_border(N, search_deg):

@@ -525,6 +525,7 @@ extern "C" {
 #include "engine_tv.inc"
 #include "engine_pdhg.inc"
 #include "engine_align.inc"
+#include "engine_tilt.inc"
 #include "engine_bin.inc"
 #include "engine_dual.inc"
 #include "engine_affine3d.inc"

@@ -427,6 +427,7 @@ class _GroupBackend:
     c_sino_moments = c_sino_xcorr = c_sino_shift = c_sino_affine = c_sino_axis_profile = c_sino_affine_normal = _no_align
     c_sino_bin = c_volume_bin = c_volume_prolong = c_volume_cross = c_volume_cross_axpy = _no_align
     c_volume_affine = c_volume_affine_axpy = c_volume_affine_normal = _no_align
+    c_volume_rot_derivative = c_sino_tilt_normal = _no_align
 
     def c_set_tilt_series(self, ptr):
         self._rows("set_sinogram", SINO_B, ptr, self.nray * self.nproj * 4)
@@ -1143,6 +1144,27 @@ class _EngineBase:
         self.be.c("sino_axis_profile", int(which), _ptr(out))
         return out
 
+    # ---- tilt-angle refinement (include/tomo_hip.h: tomo_volume_rot_derivative / tomo_sino_tilt_normal; the drivers are
+    # align.match_tilt_angles and TomoGPU.refine_tilt_angles) ------------------------------------------------------------------
+    def volume_rot_derivative(self, src=VOL_RECON, dst=VOL_TEMP):
+        """Volume ``dst`` = X d_Y f - Y d_X f of volume ``src``, slice by slice, with the pixel i * N + j at X = j - (N-1)/2,
+        Y = (N-1)/2 - i and central differences (zero in the direction that crosses the border): the volume whose projection at
+        every angle is the derivative of that projection by its angle, per radian.  ``src`` != ``dst``.  Enqueued, no wait."""
+        self._align_one_engine()
+        self.be.c("volume_rot_derivative", int(src), int(dst))
+
+    def sino_tilt_normal(self, b, g, d, margin=1):
+        """``(rd, dd, rr, count)``, each (Nproj,): per projection sum (b - g) d, sum d^2 and sum (b - g)^2 in binary64 over the samples
+        at least ``margin`` away from the image border of sinogram slots ``b`` (data), ``g`` (model) and ``d`` (derivative), and their
+        number (int64).  ``rd / dd`` is the Gauss-Newton step of the angle in radians (``align.tilt_increment``).  Nothing is written;
+        the call waits for its 4 numbers per projection."""
+        self._align_one_engine()
+        if int(margin) < 0 or 2 * int(margin) >= min(self.Ny, self.Nslice_):
+            raise ValueError("margin must not be negative and 2 * margin must stay below Nray and Nslice")
+        out = np.empty((self.Nproj, 4), np.float64)
+        self.be.c("sino_tilt_normal", int(b), int(g), int(d), int(margin), _ptr(out))
+        return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy(), out[:, 3].astype(np.int64)
+
     # ---- binning and prolongation between two engines (include/tomo_hip.h: tomo_sino_bin / tomo_volume_bin / tomo_volume_prolong) ----
     def _bin_partner(self, other):
         """Both engines are whole-volume engines of this process (the rule of the alignment calls); -> the partner's handle."""
@@ -1366,6 +1388,7 @@ class _EngineBase:
                 new.close()
             raise
         old.close()
+        self._ctor_kw = dict(angles_rad=angles_rad, A=A)      # what binned_engine builds the coarse geometry from
         if self.L_A is not None:
             self.L_A = self.get_lipschitz()
         if self.L_Aml is not None:

@@ -5,10 +5,12 @@ the matplotlib/Tk viewers of the reference are not part of the hot path.  Broken
 to the semantics of their canonical loops:
 ``fista`` is the textbook x_k = prox_TV(SIRT(y_k)) + momentum, ``asd_pocs`` follows examples/sim_ASD.py:66-94.
 """
+import ctypes
+
 import numpy as np
 
 from . import _lib, align, pytvlib
-from ._lib import S_DD, S_DIFF2, SINO_B, SINO_G, SINO_PUBLIC, SINO_USER0, VOL_RECON, VOL_TEMP, VOL_USER0, VOL_YK
+from ._lib import S_DD, S_DIFF2, SINO_B, SINO_G, SINO_PACKED, SINO_PUBLIC, SINO_USER0, VOL_RECON, VOL_TEMP, VOL_USER0, VOL_YK
 from .engine import is_tensor, multigpuengine, tomoengine
 
 
@@ -111,6 +113,7 @@ class TomoGPU:
         else:
             self.tomo = multigpuengine(self.Nslice, self.Nray, np.deg2rad(tiltAngles))
         self.verbose = verbose
+        self._tilt_deg = tiltAngles.ravel().copy()
         self.set_tilt_series(tiltSeries)
         self.recon = None
         self.cost = None
@@ -611,6 +614,99 @@ class TomoGPU:
             self.align_affine_history.append((shifts.copy(), rot.copy(), mag.copy()))
             self.align_affine_cost.append(dict(ssd=res["ssd"], ncc=res["ncc"], converged=res["converged"]))
         return self.get_alignment(), *self.get_alignment_rotation()
+
+    # ---- refinement of the tilt angles (an extension: the reference takes them as given; engine.py volume_rot_derivative /
+    # sino_tilt_normal, align.match_tilt_angles) -----------------------------------------------------------------------------
+    def get_tilt_angles(self):
+        """The tilt angles in degrees the engine projects with: those of the constructor until ``refine_tilt_angles`` (or
+        ``tomo.update_projection_angles``) replaces them."""
+        rad = getattr(self.tomo, "_ctor_kw", {}).get("angles_rad")
+        if rad is not None:
+            return np.rad2deg(np.asarray(rad, np.float64).ravel())
+        return np.array(self._tilt_deg, np.float64)
+
+    def _set_tilt_angles(self, deg):
+        """New angles for this object's engine (``update_projection_angles``: the tables are rebuilt, the volumes move over).  The
+        sinogram slots do NOT survive a rebuild, so the two the alignment state lives in -- the series in ``SINO_B`` and, once an
+        alignment call has kept it, the series as given in ``ALIGN_SLOT`` -- are carried across, as device tensors where torch sees
+        the device (a copy of bits either way).  Every kept binned object has the old angles and is dropped."""
+        t = self.tomo
+        keep = [SINO_B] + ([self.ALIGN_SLOT] if getattr(self, "_align_kept", False) else [])
+        try:
+            import torch
+            on_device = torch.cuda.is_available() and torch.cuda.device_count() > t.gpuID
+        except ImportError:
+            on_device = False
+        saved = [(s, t.get_projections_tensor(s) if on_device else t._sino_local(s)) for s in keep]
+        t.update_projection_angles(np.deg2rad(np.asarray(deg, np.float64)))
+        for s, x in saved:
+            if on_device:
+                t.be.set_tilt_series_tensor(x, SINO_PACKED, s)
+            else:
+                t.be.c("set_sinogram", int(s), x.ctypes.data_as(ctypes.c_void_p))
+        self._pyramid = {}
+
+    def refine_tilt_angles(self, Nouter=3, recon=None, damping=1.0, max_step_deg=5.0, margin=1, factor=1, apply=True):
+        """Refine the tilt angle of every projection by Gauss-Newton matching on the device.  Every pass reconstructs at the current
+        angles (``recon(self)``; default 100 SIRT iterations from zero -- NOT the 20 of the shift and affine refinements: the step
+        reads the residual b - A x, and a residual that is mostly the iteration's own remaining error points nowhere.  In binary64
+        at 32 x 32, 31 projections, +-4 degrees, 20 iterations per pass left the rms angle error at 2.1 of 2.2 degrees and then
+        raised it, 50 and 100 lowered it to 0.79 and 0.76 after one pass), forms the rotational derivative volume D x = X d_Y x - Y d_X x
+        (``volume_rot_derivative``), projects x and D x -- A (D x) is the derivative of every projection by its own angle -- and
+        reduces per projection <b - A x, A D x> and <A D x, A D x> (``align.match_tilt_angles``, ``sino_tilt_normal``).  The step of
+        angle p is their quotient times ``damping``, clipped to ``max_step_deg``; the mean of the steps of a pass is removed (a
+        common offset is a rotation of the volume about the tilt axis, which the data cannot see: ``align.tilt_increment``).  The new
+        angles are applied through ``update_projection_angles`` before the next pass.  Returns the total angles in degrees;
+        ``self.tilt_history`` holds them after every pass, ``self.tilt_cost`` per pass a dict of ``rr`` (per projection, sum of
+        (b - A x)^2 over the samples ``margin`` inside the image), ``count`` and ``data_distance`` (||A x - b|| of the pass's
+        reconstruction, BEFORE its step); ``get_tilt_angles()`` reports the current angles.  Stored shifts, rotation and
+        magnification are not touched.  ``apply=False`` leaves the engine with the angles it had on entry (they are put back).
+
+        ``factor`` = 2 or 4: reconstruction, derivative and sums run on the kept binned object (``binned``): angles do not depend on
+        resolution, and a rebuild of the coarse tables costs about 1 / factor^2 of this engine's.  Only the coarse object changes
+        angles between passes; this object's engine is rebuilt ONCE at the end.  ``recon`` is then called with the coarse object.
+        ``margin`` is in full-resolution pixels: the coarse object leaves out ``margin // factor`` of its own.
+
+        Overwrites on the engine it runs on: the reconstruction, ``VOL_TEMP`` (the derivative volume), ``SINO_G`` and sinogram slot
+        ``align.TILT_SCRATCH_SLOT``.  A rebuild carries ``SINO_B`` and ``ALIGN_SLOT`` across and drops every kept binned object.
+
+        Capture range: the step is a linearisation in the angle, good while the angle error moves the outermost detail by about a
+        pixel or two (1 degree is 0.28 pixel at the border of a 32-pixel image, 4.5 pixels at 512); errors far below a pixel at the
+        border are below what the data resolve.  One whole-volume engine only (``NotImplementedError`` otherwise)."""
+        t = self._bin_engine()
+        f = int(factor)
+        if f not in (1, 2, 4):
+            raise ValueError("factor must be 1, 2 or 4")
+        if int(Nouter) < 0:
+            raise ValueError("Nouter must not be negative")
+        if recon is None:
+            recon = lambda rec: rec.sirt(100, show_convergence=False)  # noqa: E731
+        start = self.get_tilt_angles()
+        ang = start.copy()
+        self.tilt_history, self.tilt_cost = [], []
+        moved = False                     # the engine of this object (f == 1) or of the coarse one no longer has ``start``
+        for k in range(int(Nouter)):
+            rec = self if f == 1 else self._coarse(f)          # (bins the current series into the kept coarse object)
+            recon(rec)
+            rd, dd, rr, count = align.match_tilt_angles(rec.tomo, SINO_B, VOL_RECON, margin=int(margin) // f)
+            dist = rec.tomo.data_distance()
+            ang = ang + align.tilt_increment(rd, dd, damping, max_step_deg)
+            self.tilt_history.append(ang.copy())
+            self.tilt_cost.append(dict(rr=rr, count=count, data_distance=dist))
+            if k < int(Nouter) - 1:
+                if f == 1:
+                    self._set_tilt_angles(ang)
+                else:
+                    rec.tomo.update_projection_angles(np.deg2rad(ang))     # its series is binned again by the next pass
+                moved = True
+        if apply and self.tilt_history:
+            self._set_tilt_angles(ang)
+        elif moved:
+            if f == 1:
+                self._set_tilt_angles(start)
+            else:
+                self._pyramid.pop(f, None)
+        return ang.copy()
 
     # ---- DART: discrete tomography (an extension; Batenburg & Sijbers 2011; engine.py dart_*) -------------------------------------
     def _dart_engine(self):
