@@ -164,6 +164,14 @@ def test_residual_reuse_paths(gpu, monkeypatch):
         t.set_volume(x, VOL_RECON)                                   # a fresh write: G no longer counts, the call projects
         assert _fp_launches(t, call)[1] >= 1
         assert np.array_equal(t._sino(SINO_R), reused), mode
+    # the claim a copy inherits: G = A * RECON is A * TEMP as well, until TEMP is written
+    t.set_volume(x, VOL_RECON)
+    t.be.c("data_distance_sq", VOL_RECON)
+    t.be.c("copy_volume", VOL_TEMP, VOL_RECON)
+    step = lambda: t.be.c("sirt_data", VOL_TEMP, SINO_B, 1)
+    assert _fp_launches(t, step) == (0, 0)
+    t.set_volume(x, VOL_TEMP)
+    assert _fp_launches(t, step)[1] == 1
 
 
 # ---- the headline geometry ------------------------------------------------------------------------------------------------------------

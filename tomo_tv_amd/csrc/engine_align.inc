@@ -17,15 +17,6 @@ static int al_ensure(tomo_engine *e, void **p, size_t *have, size_t bytes)
 
 #define NEED_ALIGN(e) do { NEED(e); if ((e)->comm) return fail(TOMO_ERR_STATE, "alignment runs on one whole-volume engine: this engine has a communicator"); } while (0)
 
-// a sinogram slot that is only read: allocated (zero) on first use like any slot, but asking for G does not drop its claim
-static int sino_slot_ro(tomo_engine *e, int id, float **out)
-{
-    if (id < 0 || id >= TOMO_SINO_SLOTS) return fail(TOMO_ERR_ARG, "bad sinogram id");
-    if (!e->sino[id]) { int rc = dev_alloc(e, GEOMETRY, (void **)&e->sino[id], e->sino_elems() * sizeof(float), true); if (rc) return rc; }
-    *out = e->sino[id];
-    return TOMO_OK;
-}
-
 // The tail of every call that sums in two stages (kernels_geom.hip.h) and hands the result to the caller: the second stage (finish()
 // launches it on e's stream) behind a first stage that was launched well, the copy of the result to the caller's memory, and the wait
 // for it.  With a partner the first stage read a volume of another engine: the fence back to the partner's stream follows the

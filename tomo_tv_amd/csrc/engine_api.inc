@@ -64,18 +64,32 @@ static void free_geometry(tomo_engine *e)
     e->pool.release_life(GEOMETRY);
     e->rs_ok = false; e->rs_angs_cap = 0; e->rs_angs_host.clear(); e->seg_ready = false;
     e->pdhg_begun = false;
-    e->yk_claim.valid = false;
-    e->g_prev_valid = e->mom_p_ok = e->mom.set = false;
+    e->claims.geometry_released();
     e->geometry_released = true;
+}
+
+// wait for everything the engine has enqueued (its stream, its second stream, every sub-stream): no evaluation is pending then
+static int quiesce(tomo_engine *e)
+{
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (e->aux) HIPCHK(hipStreamSynchronize(e->aux));
+    for (int u = 0; u < tomo_engine::MAX_CHAINS; ++u) if (e->sub_stream[u]) HIPCHK(hipStreamSynchronize(e->sub_stream[u]));
+    e->async_pending = false;
+    return TOMO_OK;
+}
+
+static int same_slab(const tomo_engine *a, const tomo_engine *b)
+{
+    return a->nx != b->nx || a->n != b->n || a->sx != b->sx || a->device != b->device ? fail(TOMO_ERR_ARG, "engines differ in slab shape or device") : TOMO_OK;
 }
 
 int tomo_destroy(tomo_engine *e)
 {
     if (!e) return TOMO_OK;
     (void)hipSetDevice(e->device);
-    if (e->stream) (void)hipStreamSynchronize(e->stream);
-    if (e->aux) { (void)hipStreamSynchronize(e->aux); (void)hipStreamDestroy(e->aux); (void)hipEventDestroy(e->ev_fork); (void)hipEventDestroy(e->ev_join); }
-    for (int u = 0; u < tomo_engine::MAX_CHAINS; ++u) if (e->sub_stream[u]) { (void)hipStreamSynchronize(e->sub_stream[u]); (void)hipStreamDestroy(e->sub_stream[u]); (void)hipEventDestroy(e->ev_sjoin[u]); }
+    (void)quiesce(e);                               // (teardown goes on whatever a wait answers)
+    if (e->aux) { (void)hipStreamDestroy(e->aux); (void)hipEventDestroy(e->ev_fork); (void)hipEventDestroy(e->ev_join); }
+    for (int u = 0; u < tomo_engine::MAX_CHAINS; ++u) if (e->sub_stream[u]) { (void)hipStreamDestroy(e->sub_stream[u]); (void)hipEventDestroy(e->ev_sjoin[u]); }
     comm_release(e);
     if (e->ev_sfork) (void)hipEventDestroy(e->ev_sfork);
     if (e->ev_peer) (void)hipEventDestroy(e->ev_peer);
@@ -97,10 +111,7 @@ int tomo_destroy(tomo_engine *e)
 int tomo_release_geometry(tomo_engine *e)
 {
     NEED(e);
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->aux) HIPCHK(hipStreamSynchronize(e->aux));
-    for (int u = 0; u < tomo_engine::MAX_CHAINS; ++u) if (e->sub_stream[u]) HIPCHK(hipStreamSynchronize(e->sub_stream[u]));
-    e->async_pending = false;
+    if (int rc = quiesce(e)) return rc;
     free_geometry(e);
     return TOMO_OK;
 }
@@ -108,12 +119,9 @@ int tomo_release_geometry(tomo_engine *e)
 int tomo_adopt_volumes(tomo_engine *dst, tomo_engine *src)
 {
     if (!dst || !src) return fail(TOMO_ERR_ARG, "null engine");
-    if (dst->nx != src->nx || dst->n != src->n || dst->sx != src->sx || dst->device != src->device) return fail(TOMO_ERR_ARG, "engines differ in slab shape or device");
+    if (int rc = same_slab(dst, src)) return rc;
     HIPCHK(hipSetDevice(dst->device));
-    HIPCHK(hipStreamSynchronize(src->stream));
-    if (src->aux) HIPCHK(hipStreamSynchronize(src->aux));       // nothing of src may still be reading the volumes that move
-    for (int u = 0; u < tomo_engine::MAX_CHAINS; ++u) if (src->sub_stream[u]) HIPCHK(hipStreamSynchronize(src->sub_stream[u]));
-    src->async_pending = false;
+    if (int rc = quiesce(src)) return rc;           // nothing of src may still be reading the volumes that move
     HIPCHK(hipStreamSynchronize(dst->stream));
     for (int i = 0; i < TOMO_VOL_SLOTS; ++i) {      // (an error return in here leaves the volumes before i moved: it cannot fire for engines whose volumes are their own)
         if (!src->vol[i]) continue;
@@ -121,10 +129,7 @@ int tomo_adopt_volumes(tomo_engine *dst, tomo_engine *src)
         if (src->pool.move_to(dst->pool, src->vol[i], (void **)&dst->vol[i])) return fail(TOMO_ERR_STATE, "a volume of the adopted engine is not its own");
         src->vol[i] = nullptr;                     // (its entry's slot may be the partner of a swap: move_to nulls only a slot that held the address)
     }
-    dst->old_is_recon = src->old_is_recon;
-    src->old_is_recon = false;
-    for (int i = 0; i < TOMO_VOL_SLOTS; ++i) ++dst->vol_version[i];
-    g_clear(dst);
+    dst->claims.adopt(src->claims);
     return TOMO_OK;
 }
 
@@ -292,8 +297,7 @@ int tomo_restart_recon(tomo_engine *e)
     HIPCHK(hipMemsetAsync(e->vol[TOMO_VOL_RECON], 0, e->vol_elems() * sizeof(float), e->stream));
     if (e->vol[TOMO_VOL_YK]) HIPCHK(hipMemsetAsync(e->vol[TOMO_VOL_YK], 0, e->vol_elems() * sizeof(float), e->stream));
     if (e->vol[TOMO_VOL_RECON_OLD]) HIPCHK(hipMemsetAsync(e->vol[TOMO_VOL_RECON_OLD], 0, e->vol_elems() * sizeof(float), e->stream));
-    e->old_is_recon = false;                       // every buffer is physically zero
-    ++e->vol_version[TOMO_VOL_RECON]; ++e->vol_version[TOMO_VOL_YK]; ++e->vol_version[TOMO_VOL_RECON_OLD];
+    e->claims.restarted();
     return TOMO_OK;
 }
 
@@ -305,7 +309,7 @@ int tomo_copy_volume(tomo_engine *e, int dst, int src)
     const bool g_src = g_is_projection_of(e, src);
     if ((rc = get_vol(e, dst, &d)) || (rc = get_vol_ro(e, src, &s))) return rc;
     if (d != s) HIPCHK(hipMemcpyAsync(d, s, e->vol_elems() * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
-    if (g_src && dst != src) { e->g_valid[1].vol = dst; e->g_valid[1].ver = e->vol_version[dst]; }   // G = A * src = A * dst
+    e->claims.copied(dst, src, g_src);
     return TOMO_OK;
 }
 
@@ -318,7 +322,7 @@ int tomo_forward_projection(tomo_engine *e, int vol, int sino)
     if ((rc = get_vol_ro(e, vol, &x))) return rc;
     if ((rc = sino_slot(e, sino, &g))) return rc;
     if ((rc = launch_fp_all<FP_STORE>(e, x, nullptr, g))) return rc;
-    if (sino == TOMO_SINO_G) g_set(e, vol);
+    if (sino == TOMO_SINO_G) e->claims.g_projected_from(vol);
     return TOMO_OK;
 }
 
@@ -544,9 +548,9 @@ int tomo_sino_proj_scale(tomo_engine *e, int sino, const float *div_host, const 
 int tomo_copy_volume_from(tomo_engine *dst, int dst_vol, tomo_engine *src, int src_vol)
 {
     if (!dst || !src) return fail(TOMO_ERR_ARG, "null engine");
-    if (dst->nx != src->nx || dst->n != src->n || dst->sx != src->sx || dst->device != src->device) return fail(TOMO_ERR_ARG, "engines differ in slab shape or device");
+    int rc = same_slab(dst, src); if (rc) return rc;
     HIPCHK(hipSetDevice(dst->device));
-    float *d, *s; int rc;
+    float *d, *s;
     if ((rc = get_vol(dst, dst_vol, &d)) || (rc = get_vol(src, src_vol, &s))) return rc;
     HIPCHK(hipStreamSynchronize(src->stream));
     HIPCHK(hipMemcpyAsync(d, s, dst->vol_elems() * sizeof(float), hipMemcpyDeviceToDevice, dst->stream));
@@ -560,7 +564,7 @@ int tomo_get_stream(tomo_engine *e, void **out) { if (!e || !out) return fail(TO
 static int mm_check(tomo_engine *a, tomo_engine *b, int nel)
 {
     if (!a || !b) return fail(TOMO_ERR_ARG, "null engine");
-    if (a->nx != b->nx || a->n != b->n || a->sx != b->sx || a->device != b->device) return fail(TOMO_ERR_ARG, "engines differ in slab shape or device");
+    if (int rc = same_slab(a, b)) return rc;
     if (a->stream != b->stream) return fail(TOMO_ERR_STATE, "engines must share one stream (tomo_set_stream)");
     if (nel < 1 || nel > MM_MAX_EL) return fail(TOMO_ERR_ARG, "element count out of range");
     return TOMO_OK;
@@ -630,24 +634,15 @@ int tomo_fista_momentum(tomo_engine *e, float beta)
     // the buffer recon has just left -- which, from the second step on, is also where `old` sits (old == recon then): the step
     // reads two volumes and writes one (round 2: two reads, three stores: 645 us at 512^3).  Same expression, same bits.
     { int rc_ = order_after_async(e); if (rc_) return rc_; }
-    // is the saved projection (tomo_fista_project_yk) A * (what recon_old holds now)?  recon_old was set to recon by the last step and
-    // neither has been touched since, and the projection was saved from that very recon
-    e->mom_p_ok = e->g_prev_valid && e->mom.set && e->vol_version[TOMO_VOL_RECON] == e->mom.ver_recon
-                  && e->vol_version[TOMO_VOL_RECON_OLD] == e->mom.ver_old && e->g_prev_recon_ver == e->vol_version[TOMO_VOL_RECON];
     float *x, *yk, *old; int rc;
-    const bool aliased = e->old_is_recon;
     if ((rc = get_vol_ro(e, TOMO_VOL_RECON, &x)) || (rc = get_vol_ro(e, TOMO_VOL_YK, &yk))) return rc;
-    if (aliased) old = x;                                 // recon_old's content IS recon's
-    else if ((rc = get_vol_ro(e, TOMO_VOL_RECON_OLD, &old))) return rc;
+    if ((rc = get_vol_ro(e, TOMO_VOL_RECON_OLD, &old))) return rc;   // (x itself where recon_old's content IS recon's)
     int64_t n4 = e->vol_elems() / 4;
     hipLaunchKernelGGL(k_momentum, dim3(grid_1d(n4)), dim3(256), 0, e->stream, (const f4 *)yk, (const f4 *)old, (f4 *)x, beta, n4);
     LAUNCHCHK();
-    ++e->vol_version[TOMO_VOL_RECON]; ++e->vol_version[TOMO_VOL_YK]; ++e->vol_version[TOMO_VOL_RECON_OLD];
     e->vol[TOMO_VOL_RECON] = yk;                          // the prox result r
     e->vol[TOMO_VOL_YK] = x;                              // r + beta (r - old), written over the buffer recon has left
-    e->old_is_recon = true;                               // recon_old == r, not stored
-    e->mom.beta = beta; e->mom.set = true;
-    e->mom.ver_recon = e->vol_version[TOMO_VOL_RECON]; e->mom.ver_yk = e->vol_version[TOMO_VOL_YK]; e->mom.ver_old = e->vol_version[TOMO_VOL_RECON_OLD];
+    e->claims.nesterov_step(beta);                        // recon_old == r, not stored
     return TOMO_OK;
 }
 
@@ -663,31 +658,21 @@ int tomo_fista_project_yk(tomo_engine *e, int *done)
 {
     NEED(e);
     if (done) *done = 0;
-    if (!e->fp_reuse || !g_is_projection_of(e, TOMO_VOL_RECON) || !e->mom.set) return TOMO_OK;
-    if (e->vol_version[TOMO_VOL_RECON] != e->mom.ver_recon || e->vol_version[TOMO_VOL_YK] != e->mom.ver_yk) return TOMO_OK;
+    const Claims::Linearity how = e->claims.linearity_begin(e->sino[TOMO_SINO_G] != nullptr);
+    if (how == Claims::REFUSED) return TOMO_OK;
     { int rc_ = order_after_async(e); if (rc_) return rc_; }
     int rc; float *p, *q;
     if ((rc = get_sino(e, &e->g_prev, &p)) || (rc = get_sino(e, &e->g_yk, &q))) return rc;
     const float *g = e->sino[TOMO_SINO_G];
     const int64_t n4 = (int64_t)e->sino_elems() / 4;
-    const bool have_prev = e->mom_p_ok;
-    e->yk_claim.valid = false;
-    if (have_prev) {   // q = A yk = (1 + beta) A r - beta A r_old; p = A r (the saved projection of the next step): one pass
-        hipLaunchKernelGGL(k_sino_extrapolate, dim3(grid_1d(n4)), dim3(256), 0, e->stream, (const VecOf<4>::T *)g, (VecOf<4>::T *)p, (VecOf<4>::T *)q, e->mom.beta, n4);
+    if (how == Claims::FORM) {   // q = A yk = (1 + beta) A r - beta A r_old; p = A r (the saved projection of the next step): one pass
+        hipLaunchKernelGGL(k_sino_extrapolate, dim3(grid_1d(n4)), dim3(256), 0, e->stream, (const VecOf<4>::T *)g, (VecOf<4>::T *)p, (VecOf<4>::T *)q, e->claims.beta(), n4);
         LAUNCHCHK();
     } else {
         HIPCHK(hipMemcpyAsync(p, g, e->sino_elems() * sizeof(float), hipMemcpyDeviceToDevice, e->stream));   // first step: only save A r
     }
-    e->g_prev_valid = true;
-    e->g_prev_recon_ver = e->vol_version[TOMO_VOL_RECON];
     // G is untouched: it stays A * recon, with its claim, and get_model_projections() returns what the reference's would
-    if (have_prev) {
-        e->yk_claim.valid = true; e->yk_claim.ver = e->vol_version[TOMO_VOL_YK];
-        if (done) *done = 1;
-    } else if (e->mom.beta == 0.f) {                        // yk is r, bit for bit: G is A * yk as well (the claim a copy inherits)
-        e->g_valid[1].vol = TOMO_VOL_YK; e->g_valid[1].ver = e->vol_version[TOMO_VOL_YK];
-        if (done) *done = 1;
-    }
+    if (e->claims.linearity_end(how) && done) *done = 1;
     return TOMO_OK;
 }
 
@@ -700,7 +685,7 @@ static int data_distance_on(tomo_engine *e, const Lane &ln, int vol)
     if ((rc = get_vol_ro(e, vol, &x)) || (rc = get_sino(e, &e->sino[TOMO_SINO_G], &g))) return rc;
     if ((rc = reduce_begin(e, ln))) return rc;
     if ((rc = launch_fp_all<FP_DD>(e, ln, x, e->sino[TOMO_SINO_B], g))) return rc;
-    g_set(e, vol);                                      // FP_DD also stores g = A x
+    e->claims.g_projected_from(vol);                    // FP_DD also stores g = A x
     return reduce_end(e, ln, TOMO_S_DD);
 }
 

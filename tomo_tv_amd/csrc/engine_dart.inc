@@ -118,7 +118,7 @@ int tomo_dart_smooth(tomo_engine *e, int src, int dst, float beta)
     if (e->dart_nthr < 0) return fail(TOMO_ERR_STATE, "no segmentation in hand (tomo_dart_classify)");
     if ((rc = order_after_async(e))) return rc;
     float *s, *d;
-    // dst first: where RECON_OLD still shares RECON's buffer (old_is_recon) and the two are src and dst, get_vol makes the copy real,
+    // dst first: where RECON_OLD still shares RECON's buffer (Claims::write) and the two are src and dst, get_vol makes the copy real,
     // so that two different slot ids are two different buffers by the time src is looked up -- nothing is left to refuse from here on
     if ((rc = get_vol(e, dst, &d)) || (rc = get_vol_ro(e, src, &s))) return rc;
     const int yseg = dart_yseg(e, DART_SMOOTH_TZ);

@@ -1,7 +1,7 @@
 // engine_tilt.inc -- refinement of the per-projection tilt angles: the rotational derivative of a volume and the per-projection sums
 // of the angle step (tomo_volume_rot_derivative, tomo_sino_tilt_normal).
-// Part of tomo_engine.hip (included inside its extern "C" block, after engine_align.inc, whose NEED_ALIGN, sino_slot_ro, al_ensure and
-// reduce_tail it uses); kernels: kernels_tilt.hip.h.
+// Part of tomo_engine.hip (included inside its extern "C" block, after engine_align.inc, whose NEED_ALIGN, al_ensure and reduce_tail
+// it uses); kernels: kernels_tilt.hip.h.
 //
 // One whole-volume engine only, like the other alignment calls: the derivative's stencil lies inside a slice and would not mind a
 // slab, but the sums are per projection over ALL slices, and nothing adds them across slabs.  Everything that can be refused is

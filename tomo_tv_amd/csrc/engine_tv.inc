@@ -391,7 +391,7 @@ int tomo_fgp_grad(tomo_engine *e, float lambda)
 
 int tomo_fgp_end(tomo_engine *e, int iters)
 {
-    if (e && e->fgp_target >= 0 && e->fgp_target < TOMO_VOL_SLOTS) ++e->vol_version[e->fgp_target];   // the prox result lands in the volume
+    if (e) e->claims.prox_landed(e->fgp_target);   // the prox result lands in the volume
 
     NEED(e);
     if (!e->tvg) return fail(TOMO_ERR_STATE, "tomo_fgp_begin has not been called");
@@ -553,14 +553,14 @@ int tomo_fgp_fused_last(tomo_engine *e, float lambda, int first_iteration)
     }
     LAUNCHCHK();
     std::swap(e->vol[e->fgp_target], e->fgp_q[0]);         // the prox result's buffer becomes the volume; the old one is scratch now
-    ++e->vol_version[e->fgp_target];
+    e->claims.prox_landed(e->fgp_target);
     return TOMO_OK;
 }
 
 // the last iteration only needs D (tv_fgp.cu:272), written straight over the target volume
 int tomo_fgp_fused_end(tomo_engine *e, float lambda)
 {
-    if (e && e->fgp_target >= 0 && e->fgp_target < TOMO_VOL_SLOTS) ++e->vol_version[e->fgp_target];   // the prox result lands in the volume
+    if (e) e->claims.prox_landed(e->fgp_target);   // the prox result lands in the volume
 
     NEED(e);
     if (!e->fgp_p[2]) return fail(TOMO_ERR_STATE, "tomo_fgp_fused_begin has not been called");

@@ -10,6 +10,7 @@
 #include "sysmat.h"
 #include "resident.h"
 #include "dev_pool.h"
+#include "claims.h"
 #include "sart_host.h"
 
 #include <dlfcn.h>
@@ -310,19 +311,11 @@ struct tomo_engine {
     float *comm_fgp = nullptr;                    // the engine's own planes of the fused FGP exchange when the host binds none
     float *comm_pdhg = nullptr;                   // ... and of the slab-sharded Chambolle-Pock pass (10 planes)
     double *comm_scal = nullptr;                  // TOMO_S_COUNT doubles: the all-reduced copy of the scalar buffer
-    // "the model sinogram G is A * (volume v in its present state)": set by a plain projection into G (tomo_forward_projection,
-    // tomo_data_distance_sq), inherited by a copy of v, dropped by anything else that touches G or writes v (fp_reuse, below)
-    uint64_t vol_version[TOMO_VOL_SLOTS] = {};
-    struct { int vol = -1; uint64_t ver = 0; } g_valid[2];
-    int fp_reuse = 1;
+    // which projections are in hand and whether RECON_OLD shares RECON's buffer: the write versions and every claim made on them (claims.h)
+    Claims claims;
     // FISTA: the projection of the extrapolated point by linearity (tomo_fista_project_yk)
     float *g_prev = nullptr;                      // A * (the iterate before the last Nesterov step)
     float *g_yk = nullptr;                        // A * yk formed by linearity; G itself stays A * recon (tomoengine.cpp:410-427,459)
-    struct { bool valid = false; uint64_t ver = 0; } yk_claim;   // g_yk is A * (volume YK at this write-version)
-    bool g_prev_valid = false, mom_p_ok = false;
-    uint64_t g_prev_recon_ver = 0;
-    struct { float beta = 0.f; uint64_t ver_recon = 0, ver_yk = 0, ver_old = 0; bool set = false; } mom;
-    bool old_is_recon = false;                    // RECON_OLD's content is RECON's (tomo_fista_momentum; see get_vol)
     bool geometry_released = false;               // tomo_release_geometry: only tomo_adopt_volumes / tomo_destroy remain valid
     // halos
     float *halo_lo = nullptr, *halo_hi = nullptr, *halo_lo_own = nullptr, *halo_hi_own = nullptr;
@@ -356,33 +349,24 @@ static int dev_alloc(tomo_engine *e, DevPool::Life life, void **p, size_t bytes,
 // volume for its cost and then starts a SIRT run from a copy of it (multimodal.cpp:452-470).  The engine remembers which volume
 // (slot and write-version) the model sinogram G was projected from; a SIRT / CGLS call whose volume is still that one forms its
 // first residual from G instead of projecting again -- the same kernels produced G, so the bits are the same ("fp_reuse" = 0
-// switches it off).  Conservative by construction: every write-intent access of a volume (get_vol) bumps its version, every
-// access of G through the slot accessors drops the claim, and only the two plain projections make it.
-static void g_clear(tomo_engine *e) { e->g_valid[0].vol = e->g_valid[1].vol = -1; }
-static void g_set(tomo_engine *e, int vol) { e->g_valid[0].vol = vol; e->g_valid[0].ver = e->vol_version[vol]; e->g_valid[1].vol = -1; }
-static bool g_is_projection_of(const tomo_engine *e, int vol)
-{
-    if (!e->fp_reuse || vol < 0 || vol >= TOMO_VOL_SLOTS || !e->sino[TOMO_SINO_G]) return false;
-    for (int k = 0; k < 2; ++k) if (e->g_valid[k].vol == vol && e->g_valid[k].ver == e->vol_version[vol]) return true;
-    return false;
-}
+// switches it off).  The bookkeeping is the engine's Claims record (claims.h); the accessors below are where it meets the buffers.
+static bool g_is_projection_of(const tomo_engine *e, int vol) { return e->claims.g_is_projection_of(vol, e->sino[TOMO_SINO_G] != nullptr); }
 
 // the sinogram that holds A * (volume vol as it stands), or nullptr: G through its claim, or the extrapolated point's own buffer
 static const float *projection_in_hand(const tomo_engine *e, int vol)
 {
-    if (g_is_projection_of(e, vol)) return e->sino[TOMO_SINO_G];
-    if (e->fp_reuse && vol == TOMO_VOL_YK && e->g_yk && e->yk_claim.valid && e->yk_claim.ver == e->vol_version[TOMO_VOL_YK]) return e->g_yk;
-    return nullptr;
+    const Claims::Source s = e->claims.projection_in_hand(vol, e->sino[TOMO_SINO_G] != nullptr, e->g_yk != nullptr);
+    return s == Claims::FROM_G ? e->sino[TOMO_SINO_G] : s == Claims::FROM_G_YK ? e->g_yk : nullptr;
 }
 
 // After a Nesterov step recon_old == recon (tomoengine.cpp:381-384 copies the prox result into both).  The step keeps that as a
-// FLAG instead of a second store (old_is_recon: the logical content of RECON_OLD is RECON's; its own buffer is stale), so the
+// FLAG instead of a second store (Claims::nesterov_step: the logical content of RECON_OLD is RECON's; its own buffer is stale), so the
 // step reads two volumes and writes one.  Whoever may WRITE recon, or touches recon_old, goes through get_vol, which first makes
 // the copy real; readers of recon use get_vol_ro and leave the flag alone.
 static int get_vol_ro(tomo_engine *e, int id, float **out)
 {
     if (id < 0 || id >= TOMO_VOL_SLOTS) return fail(TOMO_ERR_ARG, "bad volume id");
-    if (id == TOMO_VOL_RECON_OLD && e->old_is_recon) id = TOMO_VOL_RECON;     // read-only view of the same content
+    id = e->claims.read_slot(id);
     if (!e->vol[id]) { int rc = dev_alloc(e, ENGINE, (void **)&e->vol[id], e->vol_elems() * sizeof(float), true); if (rc) return rc; }
     *out = e->vol[id];
     return TOMO_OK;
@@ -391,14 +375,7 @@ static int get_vol_ro(tomo_engine *e, int id, float **out)
 static int get_vol(tomo_engine *e, int id, float **out)
 {
     if (id < 0 || id >= TOMO_VOL_SLOTS) return fail(TOMO_ERR_ARG, "bad volume id");
-    ++e->vol_version[id];                               // the caller may write it
-    // A REPRODUCIBILITY choice, not a staleness fix: g_yk is still exactly A * YK after a write to RECON (neither YK nor g_yk was touched;
-    // a write to YK drops the claim through the version above).  But g_yk was formed by linearity and does not have the bits of a
-    // projection of YK, and a run in which the caller steps in between tomo_fista_project_yk and the next tomo_sirt on YK is required to
-    // give the bits of "fp_reuse" = 0 (tests/test_gpu_sequences.py, section (c)).  The FISTA driver never writes RECON there: no cost.
-    if (id == TOMO_VOL_RECON) e->yk_claim.valid = false;
-    if (e->old_is_recon && (id == TOMO_VOL_RECON || id == TOMO_VOL_RECON_OLD)) {
-        e->old_is_recon = false;
+    if (e->claims.write(id)) {                          // RECON_OLD shared RECON's buffer until now: make the copy real
         float *src, *dst; int rc;
         if ((rc = get_vol_ro(e, TOMO_VOL_RECON, &src)) || (rc = get_vol_ro(e, TOMO_VOL_RECON_OLD, &dst))) return rc;
         HIPCHK(hipMemcpyAsync(dst, src, e->vol_elems() * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
@@ -408,7 +385,7 @@ static int get_vol(tomo_engine *e, int id, float **out)
 
 static int get_sino(tomo_engine *e, float **slot, float **out)
 {
-    if (slot == &e->sino[TOMO_SINO_G]) g_clear(e);      // whoever asks for G may overwrite it
+    if (slot == &e->sino[TOMO_SINO_G]) e->claims.g_touched();
     if (!*slot) { int rc = dev_alloc(e, GEOMETRY, (void **)slot, e->sino_elems() * sizeof(float), true); if (rc) return rc; }
     *out = *slot;
     return TOMO_OK;
@@ -418,6 +395,15 @@ static int sino_slot(tomo_engine *e, int id, float **out)
 {
     if (id < 0 || id >= TOMO_SINO_SLOTS) return fail(TOMO_ERR_ARG, "bad sinogram id");
     return get_sino(e, &e->sino[id], out);
+}
+
+// a sinogram slot that is only read: allocated (zero) on first use like any slot, but asking for G does not drop its claim
+static int sino_slot_ro(tomo_engine *e, int id, float **out)
+{
+    if (id < 0 || id >= TOMO_SINO_SLOTS) return fail(TOMO_ERR_ARG, "bad sinogram id");
+    if (!e->sino[id]) { int rc = dev_alloc(e, GEOMETRY, (void **)&e->sino[id], e->sino_elems() * sizeof(float), true); if (rc) return rc; }
+    *out = e->sino[id];
+    return TOMO_OK;
 }
 
 static int get_scratch(tomo_engine *e, float **slot, float **out)
