@@ -184,8 +184,12 @@ static int finish_create_impl(tomo_engine *e, Coo &m, tomo_engine **out)
                 build_sart_resident(e->n, e->np, t, e->rs_cus, R);
                 // every workgroup of a launch must be on the chip at once: the runtime's own count of workgroups per CU for this kernel
                 // (registers, LDS) has to cover the launch; and the chunks of a sweep that could not finish go to the tile chain
+                // (a runtime that cannot answer admits nothing: the sweep is an option, the engine is not -- rs_ok stays false)
                 int per_cu = 0;
-                if (R.ok) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_sart_resident, RS_THREADS, 0));
+                if (R.ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_sart_resident, RS_THREADS, 0) != hipSuccess) {
+                    (void)hipGetLastError();
+                    per_cu = 0;
+                }
                 if (R.ok && e->st_ok && (int64_t)per_cu * e->rs_cus >= R.ntiles) {
                     e->rs_ntiles = R.ntiles; e->rs_tiles = R.tiles; e->rs_rpt = R.rpt;
                     e->rs_groups = std::max(1, std::min(per_cu * e->rs_cus / R.ntiles, e->sxc / 64));

@@ -60,14 +60,18 @@ struct RsArgs {
     int n, sx, np, ntiles, tiles, rpt, steps, chunk0, nchunk;
     unsigned epoch0, spin_limit;
     float beta;
-    long long *prof;                // measurement builds (-DRS_PROF): 8 phase totals per workgroup, in ticks of s_memrealtime (100 MHz)
+    long long *prof;                // measurement builds (-DRS_PROF): 8 phase totals per workgroup, in ticks of s_memrealtime (100 MHz); from
+                                    // [2176]: per workgroup {sum, count} of the projection phase (first wave starts BP .. last wave ends FP)
 };
 #ifdef RS_PROF
 #define RS_STAMP(q) { const long long now_ = (long long)__builtin_amdgcn_s_memrealtime(); if (wave == 0) tacc[q] += now_ - tprev; tprev = now_; }
 #define RS_TL(q) { if (k == 40 && blockIdx.x == 37 && lane == 0) rs_args()->prof[2048 + wave * 8 + (q)] = (long long)__builtin_amdgcn_s_memrealtime(); }
+// the projection phase of a step: from the first wave that starts its back projection to the last wave that ends its forward projection
+#define RS_PH(slot, op) { if (lane == 0) op(&rs_tp[k & 1][slot], (unsigned long long)__builtin_amdgcn_s_memrealtime()); }
 #else
 #define RS_STAMP(q)
 #define RS_TL(q)
+#define RS_PH(slot, op)
 #endif
 
 __device__ __forceinline__ rs_u64 rs_gld(const rs_u64 *p)
@@ -126,17 +130,19 @@ __device__ __forceinline__ bool rs_commit(unsigned *w, unsigned base, unsigned n
 }
 
 // ---- the two static loops over a wave's 64 pixels --------------------------------------------------------------------------------
-// Cells arrive 16 pixels (64 dwords = all of s[36:99]) at a time: four s_load_dwordx16, one wait, sixteen pixels of work.  A scalar
-// load is ~0.2 us from the L2 whatever its size and only lgkmcnt(0) is a safe wait (scalar loads return out of order), so what
-// counts is round trips per pass: double-buffered sets of 8 pixels (the first form: 8 round trips, each hidden behind 8 pixels = 0.03
-// to 0.07 us of this wave's own work) took 1.4 us (back projection) and 2.1 us (forward projection) per wave and pass; one set of 16
-// pixels has four, and the other three waves of the SIMD fill them (profiles/r05_resident_sweep.md).
-// SB = first SGPR of the set (36), K = pixel inside the batch, Q = pixel of the block.
-#define RS_LD(OFF)                                                                                        \
-    "s_load_dwordx16 s[36:51], %[cp], " #OFF "\n"                                                         \
-    "s_load_dwordx16 s[52:67], %[cp], " #OFF "+0x40\n"                                                    \
-    "s_load_dwordx16 s[68:83], %[cp], " #OFF "+0x80\n"                                                    \
-    "s_load_dwordx16 s[84:99], %[cp], " #OFF "+0xc0\n"
+// Cells arrive in two alternating sets of 8 pixels (32 dwords each: set A = s[36:67], set B = s[68:99]): while one set is in use
+// the other is in flight.  A scalar load is ~0.2 us from the L2 whatever its size and only lgkmcnt(0) is a safe wait (scalar loads
+// return out of order), so a set is requested right after the wait that delivered the other one and is waited for after that other
+// set's 8 pixels.  8 pixels of a wave's own work are 0.03 to 0.08 us -- what hides the round trip is the work of the other three waves
+// of the SIMD in between, and that needs the four waves to advance TOGETHER: the arbiter prefers the oldest ready wave, which then
+// runs ahead alone with every round trip exposed and leaves the youngest to do the same at the end of the phase (one set of 16 pixels
+// and no priorities, rounds 5 and 6: the phase took 5.8 us, the last wave's forward projection ran alone; profiles/
+// resident_projection_phase.md).  So a wave's priority falls as it advances (s_setprio 3, 2 in the back projection, 1, 0 in the forward
+// projection): whoever is behind goes first.  Each of the two alone gains less than both (same file).
+// SB = first SGPR of the set (36 or 68), K = pixel inside the set, Q = pixel of the block.
+#define RS_LDA(OFF) "s_load_dwordx16 s[36:51], %[cp], " #OFF "\n" "s_load_dwordx16 s[52:67], %[cp], " #OFF "+0x40\n"
+#define RS_LDB(OFF) "s_load_dwordx16 s[68:83], %[cp], " #OFF "\n" "s_load_dwordx16 s[84:99], %[cp], " #OFF "+0x40\n"
+#define RS_PRIO(P) "s_setprio " #P "\n"
 #define RS_IDX(SB, K) "s_set_gpr_idx_idx s[" #SB "+4*" #K "]\n"
 // back-projection, cell {s0, w0, w1, inv}; index mode on SRC1; rows in v[32:47] (v46 = v47 = 0: where a pixel without rays points)
 #define RS_BP1(SB, K, Q)                                                                                  \
@@ -152,12 +158,15 @@ __device__ __forceinline__ bool rs_commit(unsigned *w, unsigned base, unsigned n
     RS_IDX(SB, K)                                                                                         \
     "v_fma_f32 v32, s[" #SB "+4*" #K "+1], v[64+" #Q "], v32\n"                                           \
     "v_fma_f32 v33, s[" #SB "+4*" #K "+2], v[64+" #Q "], v33\n"
-#define RS_BATCH(OP, B)                                                                                   \
-    OP(36, 0, 16*B+0) OP(36, 1, 16*B+1) OP(36, 2, 16*B+2) OP(36, 3, 16*B+3) OP(36, 4, 16*B+4) OP(36, 5, 16*B+5) OP(36, 6, 16*B+6) OP(36, 7, 16*B+7) \
-    OP(36, 8, 16*B+8) OP(36, 9, 16*B+9) OP(36, 10, 16*B+10) OP(36, 11, 16*B+11) OP(36, 12, 16*B+12) OP(36, 13, 16*B+13) OP(36, 14, 16*B+14) OP(36, 15, 16*B+15)
 #define RS_WAIT "s_waitcnt lgkmcnt(0)\n"
-#define RS_SWEEP(OP)                                                                                      \
-    RS_BATCH(OP, 0) RS_LD(0x100) RS_WAIT RS_BATCH(OP, 1) RS_LD(0x200) RS_WAIT RS_BATCH(OP, 2) RS_LD(0x300) RS_WAIT RS_BATCH(OP, 3)
+// set H (0..7) of a pass = pixels 8 H .. 8 H + 7 of the block, 128 bytes of the wave's 1-KB cell block; P1 = the priority of the pass's second half
+#define RS_HALF(OP, SB, H) OP(SB, 0, 8*H+0) OP(SB, 1, 8*H+1) OP(SB, 2, 8*H+2) OP(SB, 3, 8*H+3) OP(SB, 4, 8*H+4) OP(SB, 5, 8*H+5) OP(SB, 6, 8*H+6) OP(SB, 7, 8*H+7)
+#define RS_HEAD RS_LDA(0x000) RS_WAIT RS_LDB(0x080)
+#define RS_SWEEP(OP, P1)                                                                                  \
+    RS_HALF(OP, 36, 0) RS_WAIT RS_LDA(0x100) RS_HALF(OP, 68, 1) RS_WAIT RS_LDB(0x180)                     \
+    RS_HALF(OP, 36, 2) RS_WAIT RS_LDA(0x200) RS_HALF(OP, 68, 3) RS_WAIT RS_LDB(0x280) RS_PRIO(P1)         \
+    RS_HALF(OP, 36, 4) RS_WAIT RS_LDA(0x300) RS_HALF(OP, 68, 5) RS_WAIT RS_LDB(0x380)                     \
+    RS_HALF(OP, 36, 6) RS_WAIT RS_HALF(OP, 68, 7)
 // Register assumptions of the asm blocks (x in v[64:127], rows / sums in v[32:47], v[48:59] scratch, s[33], s[36:99] cells; 128 VGPRs at
 // amdgpu_waves_per_eu(4, 4)): written against and verified on ROCm 7.2.0 (hipcc = AMD clang 20, gfx950).  Another toolchain: a register the
 // compiler needs elsewhere is a BUILD error (constraint conflict); tools/experiments/resident_probe.hip replays the kernel bit for bit against a
@@ -235,6 +244,11 @@ void k_sart_resident(const RsArgs unused_by_name)
     __shared__ float rs_sbuf[RS_WAVES][64];              // a reducer wave's share of a ray sum (4 KB)
     __shared__ float rs_dump[RS_WAVES][64];              // where the cell prefetches land (never read)
     __shared__ int rs_dirty, rs_go, rs_store;                   // a wave of this workgroup left a spin without its data; the chunk's verdict
+#ifdef RS_PROF
+    __shared__ unsigned long long rs_tp[2][2];                  // per step parity: earliest start of a back projection, latest end of a forward projection
+    __shared__ long long rs_tacc[2];                            // {sum, count} of the phases (kept in the LDS: the registers are full)
+    if (threadIdx.x == 0) rs_tacc[0] = rs_tacc[1] = 0;
+#endif
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     v32f xlo, xhi;
@@ -253,6 +267,9 @@ void k_sart_resident(const RsArgs unused_by_name)
         const uint32_t voff = (uint32_t)(chunk * 64 + lane) * 4u;
         {   // a sweep that has given up touches no further chunk (the host redoes what did not commit)
             if (threadIdx.x == 0) { rs_dirty = 0; rs_go = rs_abort_ld(rs_args()->abort_word) == 0 ? 1 : 0; }
+#ifdef RS_PROF
+            if (threadIdx.x == 0) { rs_tp[0][0] = rs_tp[1][0] = ~0ull; rs_tp[0][1] = rs_tp[1][1] = 0ull; }
+#endif
             __syncthreads();
             if (rs_go == 0) break;
         }
@@ -346,12 +363,14 @@ void k_sart_resident(const RsArgs unused_by_name)
                 rs_touch(A, tile, wave, lane, k + 2 < steps ? rs_angle(A, k + 2) : -1, rs_dump[wave]);
                 RS_STAMP(1)
                 RS_TL(1)
+                RS_PH(0, atomicMin)
                 asm volatile("s_mov_b32 s33, m0\n"
-                             RS_LD(0x000)
-                             RS_WAIT
+                             RS_PRIO(3)
+                             RS_HEAD
                              "s_set_gpr_idx_on s36, gpr_idx(SRC1)\n"
-                             RS_SWEEP(RS_BP1)
+                             RS_SWEEP(RS_BP1, 2)
                              "s_set_gpr_idx_off\n"
+                             RS_PRIO(0)
                              "s_mov_b32 m0, s33\n"
                              : "+{v[64:95]}"(xlo), "+{v[96:127]}"(xhi), "+{v[32:47]}"(rr)
                              : [cp] "s"(cp), [beta] "s"(beta)
@@ -374,10 +393,10 @@ void k_sart_resident(const RsArgs unused_by_name)
                 for (int s = 0; s < 16; ++s) rr[s] = 0.f;
                 const uint4 *cp = A->cell + (((size_t)a * A->ntiles + tile) * RS_WAVES + wave) * 64;
                 asm volatile("s_mov_b32 s33, m0\n"
-                             RS_LD(0x000)
-                             RS_WAIT
+                             RS_PRIO(1)
+                             RS_HEAD
                              "s_set_gpr_idx_on s36, gpr_idx(SRC2,DST)\n"
-                             RS_SWEEP(RS_FP1)
+                             RS_SWEEP(RS_FP1, 0)
                              "s_set_gpr_idx_off\n"
                              "s_mov_b32 m0, s33\n"
                              : "+{v[64:95]}"(xlo), "+{v[96:127]}"(xhi), "+{v[32:47]}"(rr)
@@ -385,9 +404,16 @@ void k_sart_resident(const RsArgs unused_by_name)
                              : RS_CLOBBERS);
                 RS_STAMP(3)
                 RS_TL(3)
+                RS_PH(1, atomicMax)
 #pragma unroll
                 for (int s = 0; s < 16; ++s) rs_pbuf[wave][s][lane] = rr[s];
                 __syncthreads();
+#ifdef RS_PROF
+                if (threadIdx.x == 0) {      // (the slot's next writers are two steps away, behind this step's and the next step's barrier)
+                    if (k >= 0) { rs_tacc[0] += (long long)(rs_tp[k & 1][1] - rs_tp[k & 1][0]); rs_tacc[1] += 1; }
+                    rs_tp[k & 1][0] = ~0ull; rs_tp[k & 1][1] = 0ull;
+                }
+#endif
                 rs_u64 *pb = A->pb + ((size_t)grp * A->ntiles + tile) * RS_MAXWIN * 64 + lane;
                 // the tile's sum of window ray i = the block sums its list names (bytes wave << 4 | slot = row of rs_pbuf), in wave order;
                 // the list is padded to eight with a row that is always zero.  (The first form asked all sixteen waves "is ray i in
@@ -522,6 +548,7 @@ void k_sart_resident(const RsArgs unused_by_name)
     if (threadIdx.x == 0) {
         RsArgsP A = rs_args();
         for (int q = 0; q < 8; ++q) A->prof[blockIdx.x * 8 + q] = tacc[q];
+        A->prof[2176 + blockIdx.x * 2] = rs_tacc[0]; A->prof[2176 + blockIdx.x * 2 + 1] = rs_tacc[1];
         if (blockIdx.x == 0) { A->prof[2048 + 126] = (long long)__builtin_amdgcn_s_memtime() - clk0; A->prof[2048 + 127] = (long long)__builtin_amdgcn_s_memrealtime() - rt0; }
     }
 #endif
@@ -540,10 +567,13 @@ void k_sart_resident(const RsArgs unused_by_name)
 #undef RS_CLOB4
 #undef RS_SWEEP
 #undef RS_WAIT
-#undef RS_BATCH
+#undef RS_HEAD
+#undef RS_HALF
 #undef RS_FP1
 #undef RS_IDX
 #undef RS_BP1
-#undef RS_LD
+#undef RS_PRIO
+#undef RS_LDB
+#undef RS_LDA
 
 }  // namespace tomo

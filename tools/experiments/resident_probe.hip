@@ -68,7 +68,7 @@ int main(int argc, char **argv)
     A.commit = dcommit; A.done_host = hdone; A.seq = 0; A.commit_base = 0; A.test_fail = 0;
     std::vector<int> hang(steps); for (int k = 0; k < steps; ++k) hang[k] = k % P;
     int *dang; CK(hipMalloc(&dang, steps * 4)); CK(hipMemcpy(dang, hang.data(), steps * 4, hipMemcpyHostToDevice)); A.angs = dang;
-    long long *dprof; CK(hipMalloc(&dprof, (2048 + 128) * 8)); CK(hipMemset(dprof, 0, (2048 + 128) * 8)); A.prof = dprof;
+    long long *dprof; CK(hipMalloc(&dprof, (2176 + 512) * 8)); CK(hipMemset(dprof, 0, (2176 + 512) * 8)); A.prof = dprof;
     std::vector<float> tk0;
     float *dtk = nullptr;
     if (tracked) {
@@ -114,6 +114,12 @@ int main(int argc, char **argv)
         }
         { std::vector<long long> ck(2); CK(hipMemcpy(ck.data(), dprof + 2048 + 126, 16, hipMemcpyDeviceToHost));
           printf("CLOCK s_memtime %lld ticks over %.1f us = %.0f MHz\n", ck[0], ck[1] * 0.01, ck[0] / (ck[1] * 0.01)); }
+        {   // the projection phase: per step and workgroup, first wave starts its back projection .. last wave ends its forward projection
+            std::vector<long long> ph(512); CK(hipMemcpy(ph.data(), dprof + 2176, 512 * 8, hipMemcpyDeviceToHost));
+            double sum = 0, cnt = 0, lo = 1e30, hi = 0;
+            for (int w = 0; w < nwg && w < 256; ++w) if (ph[w * 2 + 1] > 0) { const double m = ph[w * 2] * 0.01 / ph[w * 2 + 1]; sum += ph[w * 2]; cnt += ph[w * 2 + 1]; lo = std::min(lo, m); hi = std::max(hi, m); }
+            if (cnt > 0) printf("PHASE projection (first BP start .. last FP done), us per step: mean %.2f over %.0f steps x workgroups of the last rep (workgroup means %.2f .. %.2f); issue alone 3.0\n", sum * 0.01 / cnt, cnt, lo, hi);
+        }
         printf("PROF us per angle (wave 0, mean over workgroups): wait rows %.2f | barrier+rows->regs %.2f | BP %.2f | FP %.2f | block sums->LDS, barrier, tile sums, publish %.2f | reducer poll %.2f | barrier, final, publish %.2f | loop head %.2f\n",
                av[0], av[1], av[2], av[3], av[4], av[5], av[6], av[7]);
     }
