@@ -65,7 +65,11 @@ def gamma(m):
 class Matrix:
     """The engine's system matrix for ``N`` rays and the tilt angles (degrees) in the order given, in binary64.
 
-    ``rows`` / ``cols`` index the sinogram row ``angle * N + ray`` and the pixel ``y * N + z``."""
+    ``rows`` / ``cols`` index the sinogram row ``angle * N + ray`` and the pixel ``y * N + z``.
+
+    ``A=``: float32 (3, nnz) triplets in place of the engine's own matrix.  They must be CANONICAL -- no (row, col) twice (every
+    sum below would count both assignments, where the engine and the oracle keep the last one); explicit zero weights and rows in
+    any order are fine.  ``tests/user_matrices.py: canonical()`` makes any triplet list so; ``duplicates`` counts what is left."""
 
     def __init__(self, N, angles_deg, A=None):
         if A is None:
@@ -296,14 +300,14 @@ class Matrix:
         return x.reshape(len(x), self.N, self.N)
 
 
-    def art(self, x, b, beta):
-        """One Kaczmarz sweep over the rows in natural order in binary64 (the formula of ``orc_art``): x += beta a_j (b_j - a_j x) /
-        |a_j|^2 for rows with |a_j|^2 > 0, then the clamp at 0."""
+    def art(self, x, b, beta, order=None):
+        """One Kaczmarz sweep over the rows in natural order (or in ``order``, a sequence of row numbers) in binary64 (the formula of
+        ``orc_art``): x += beta a_j (b_j - a_j x) / |a_j|^2 for rows with |a_j|^2 > 0, then the clamp at 0."""
         x = np.array(x, np.float64).reshape(len(x), self.ncol)
         b = np.asarray(b, np.float64).reshape(len(x), self.nrow)
         beta = float(np.float32(beta))
         o, p, _ = self._r
-        for j in range(self.nrow):
+        for j in (range(self.nrow) if order is None else np.asarray(order, np.int64)):
             if not self.rowinner[j] > 0:
                 continue
             e = o[p[j]:p[j + 1]]

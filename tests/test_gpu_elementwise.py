@@ -48,7 +48,7 @@ import oracle
 import ref64
 from tomo_tv_amd import _lib
 from tomo_tv_amd._lib import S_DIFF, VOL_ORIGINAL, VOL_RECON, VOL_TEMP
-from tomo_tv_amd.engine import ctvlib, system_matrix, tomoengine
+from tomo_tv_amd.engine import _ptr, ctvlib, system_matrix, tomoengine
 
 pytestmark = pytest.mark.gpu
 
@@ -89,12 +89,16 @@ def matrix(gid):
     return _MATRIX[gid]
 
 
-def engine(monkeypatch, ang, N, Nx, fp=None, bp=None):
-    """A tomoengine running the named FP / BP form (asserted)."""
+def engine(monkeypatch, ang, N, Nx, fp=None, bp=None, A=None):
+    """A tomoengine running the named FP / BP form (asserted); ``A``: a ctvlib engine of that matrix (load_A) instead."""
     if fp in ("list", "strip"):
         monkeypatch.setenv("TOMO_FP_STRIP", "1")
         monkeypatch.setenv("TOMO_FP_LIST", "1" if fp == "list" else "0")
-    t = tomoengine(Nx, N, np.asarray(ang) * np.pi / 180)
+    if A is None:
+        t = tomoengine(Nx, N, np.asarray(ang) * np.pi / 180)
+    else:
+        t = ctvlib(Nx, N, len(ang))
+        t.load_A(A)
     monkeypatch.delenv("TOMO_FP_STRIP", raising=False)
     monkeypatch.delenv("TOMO_FP_LIST", raising=False)
     if fp in ("tile", "tile1", "tile2", "tile3"):
@@ -164,6 +168,7 @@ def dense_fp_check(t, M, Nx, orc_slices=None):
     y = fp_of(t, x)
     sl = np.arange(Nx) if orc_slices is None else np.asarray(orc_slices)
     y64, bound, ax = M.fp_bound(x[sl])
+    print(f"ratio FP dense: {ref64.ratio(y[sl], y64, bound):.3f}")
     ref64.assert_within("FP", y[sl], y64, bound)
     orc = oracle.ctvlib(len(sl), M.N, M.P)
     orc.A = oracle.CSR(M.nrow, M.ncol, *M.csr())
@@ -177,6 +182,7 @@ def dense_bp_check(t, M, Nx, orc_slices=None):
     v = bp_of(t, r)
     sl = np.arange(Nx) if orc_slices is None else np.asarray(orc_slices)
     v64, bound, ar = M.bp_bound(r[sl])
+    print(f"ratio BP dense: {ref64.ratio(v[sl], v64, bound):.3f}")
     ref64.assert_within("BP", v[sl], v64, bound)
     orc = oracle.ctvlib(len(sl), M.N, M.P)
     orc.A = oracle.CSR(M.nrow, M.ncol, *M.csr())
@@ -351,19 +357,35 @@ SART_CASES = [("lin70", "resident"), ("lin70", "tile"), ("lin70", "angle"), ("ax
               ("neg150", "tile")]
 
 
-def _sart_check(t, M, x, b, form, sl, beta=0.7):
+def _sart_check(t, M, x, b, form, sl, beta=0.7, order=None):
+    """One sweep (tomo_sart: what ``tomoengine.SART`` calls) in the named form, the angles in ``order`` (None: as given).  Beyond the
+    three public forms: "coop" / "coop_own" = the tile chain with the residual rows formed inside the next tile step ("sart_coop";
+    _own: every workgroup forms its own rows), "walk" = the fused ray-walk step ("sart_tile" = 0; reported as ANGLE)."""
     if form == "resident":
         t.set_option("sart_resident", 1)
-    elif form == "tile":
+    elif form in ("tile", "coop", "coop_own"):
         t.set_option("sart_resident", 0)
+        t.set_option("sart_coop", 0 if form == "tile" else 1)
+        if form == "coop_own":
+            t.set_option("sart_coop_spin", -1)
+    elif form == "walk":
+        t.set_option("sart_resident", 0)
+        t.set_option("sart_tile", 0)
     else:
         t.set_option("sart_fused", 0)
-    code = {"resident": SART_RESIDENT, "tile": SART_TILE, "angle": SART_ANGLE}[form]
+    code = {"resident": SART_RESIDENT, "tile": SART_TILE, "coop": SART_TILE, "coop_own": SART_TILE, "walk": SART_ANGLE, "angle": SART_ANGLE}[form]
     assert t.get_option("form_sart") == code, (form, t.get_option("form_sart"))
     t.set_tilt_series(b)
     t.set_volume(x, VOL_RECON)
-    n = launches(t, _lib.K_SART_RESIDENT, lambda: t.SART(beta, 1))
+    o = None if order is None else np.ascontiguousarray(order, np.int32)
+    count = {}
+
+    def sweep():
+        count["fused"] = launches(t, _lib.K_SART_FUSED, lambda: t.be.c("sart", VOL_RECON, float(beta), 1, None if o is None else _ptr(o)))
+    n = launches(t, _lib.K_SART_RESIDENT, sweep)
     got = t.get_volume()[sl]
+    if form == "walk":
+        assert count["fused"] > 0                       # fused ray-walk steps, not one FP + one BP launch per angle
     if form == "resident":
         assert n == 1 and t.get_option("sart_resident_fallbacks") == 0
     else:
@@ -372,8 +394,11 @@ def _sart_check(t, M, x, b, form, sl, beta=0.7):
     orc.A = oracle.CSR(M.nrow, M.ncol, *M.csr())
     orc.set_tilt_series(b[sl])
     orc.recon[:] = x[sl]
-    orc.SART(beta, 1)
-    ref64.assert_seq(f"SART {form}", got, orc.recon, M.sart(x[sl], b[sl], beta))
+    orc.SART(beta, 1, order=o)
+    ref = M.sart(x[sl], b[sl], beta, order=o)
+    print(f"ratio SART sweep: {ref64.ratio(got, ref, ref64.seq_bound(orc.recon, ref)):.3f}")
+    ref64.assert_seq(f"SART {form}", got, orc.recon, ref)
+    return got, orc.recon
 
 
 @pytest.mark.parametrize("gid,form", SART_CASES, ids=[f"{g}-sart_{f}" for g, f in SART_CASES])

@@ -13,8 +13,8 @@ instances that carry it:
   strip, list         TOMO_FP_STRIP / TOMO_FP_LIST                        128                  lin70, axes45
   list (headline)     N = 512, P = 90                                     128                  DD and POISSON only
 
-The engine's parallel-ray matrices have no empty rows on these geometries (every ray meets the image), so the rowsum == 0 rule of
-RESID_NORM is not reached here.  Reuse paths (k_sino_resid): tomo_sirt after a data distance of the same volume, and the CGLS restart.
+The engine's parallel-ray matrices have no empty rows on these geometries (every ray meets the image): the rowsum == 0 rule of
+RESID_NORM is reached in tests/test_gpu_user_matrix.py, on matrices with empty and negative-sum rays.  Reuse paths (k_sino_resid): tomo_sirt after a data distance of the same volume, and the CGLS restart.
 
 Reductions (S_DIFF, S_RMSE, S_L1, S_TV, S_GNORM) on volumes with sentinels (``ref64.with_sentinels``): each test asserts that
 dropping or doubling any sentinel's term moves the sum by more than 10 bounds (S_GNORM: sentinels on a constant volume, since the
