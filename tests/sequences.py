@@ -413,6 +413,9 @@ CLAIM_VOLUME_WRITERS = ("tomo_dart_restore", "tomo_dart_segment", "tomo_dart_arm
                         "tomo_adopt_volumes")
 CLAIM_SINO_WRITERS = ("tomo_sino_shift", "tomo_sino_affine", "tomo_sino_bin", "tomo_set_sinogram_device")
 LANE_REDUCERS = ("tomo_dart_classify", "tomo_dart_class_stats", "tomo_sino_moments", "tomo_sino_xcorr", "tomo_sino_axis_profile")
+# section (c), refused calls: writers that refuse a call for the engine's state (no begin) -- entry (without "tomo_") -> arguments; the
+# refusal comes before any claim changes, so the step that follows behaves as on an engine that never made the call
+REFUSED_WITHOUT_BEGIN = {"fgp_end": (3,), "fgp_fused_end": (0.02,)}
 
 # ---- the closure table: every `int tomo_*(tomo_engine *...)` of include/tomo_hip.h -------------------------------------------------------
 # name -> (classes, note).  Classes: "vol" writes a volume slot, "sino" writes a sinogram slot, "reduce" reduction user, "stage" user

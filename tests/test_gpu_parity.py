@@ -1186,13 +1186,17 @@ def test_each_lane_projects_through_its_own_scratch(gpu, monkeypatch, form):
 def test_tv_gradient_kernels_are_bit_identical(gpu, N, Nx):
     """Register march without row rotation (k_tv_march4, default), register march (k_tv_grad_reg), LDS march (k_tv_grad_lds)
     and the TV value they fold into the first pass: the same arithmetic in the same order, so three descent steps leave the
-    same bits; the direct-global stencil (4 sqrt + 4 div per voxel) agrees to rounding."""
+    same bits; the direct-global stencil (4 sqrt + 4 div per voxel) agrees to rounding.  "tv_recompute" = 0 (k_tv_grad_reg<8> stores g,
+    k_tv_update applies it) is the same arithmetic again; "tv_lds" = 16 (k_tv_grad_lds<16>) leaves the default's bits too and takes its
+    TV value from the direct stencil (k_tv_value), so that value is held to the direct form's bound."""
     x = np.random.default_rng(N + Nx).random((Nx, N, N), dtype=np.float32)
     out = {}
-    for opt in (1, "reg", 8, 0):
+    for opt in (1, "reg", "store", 8, 16, 0):
         t = tomoengine(Nx, N, np.array([10.0, 40.0]) * np.pi / 180)
         if opt == "reg":
             t.set_option("tv_march4", 0)
+        elif opt == "store":
+            t.set_option("tv_recompute", 0)
         else:
             t.set_option("tv_lds", opt)
         t.set_volume(x, VOL_RECON)
@@ -1201,6 +1205,11 @@ def test_tv_gradient_kernels_are_bit_identical(gpu, N, Nx):
     assert np.array_equal(out[1][1], out[8][1]) and out[1][0] == out[8][0] and out[1][2] == out[8][2]
     assert np.array_equal(out[1][1], out["reg"][1]) and out[1][0] == out["reg"][0]
     assert np.abs(out[1][1] - out[0][1]).max() < 1e-6 and abs(out[1][0] - out[0][0]) <= 1e-6 * out[0][0]
+    print(f"tv_recompute=0: volume equal {np.array_equal(out[1][1], out['store'][1])}, tv {out['store'][0]!r} / {out[1][0]!r}; "
+          f"tv_lds=16: volume max |diff| {np.abs(out[1][1] - out[16][1]).max():.3e}, tv rel {abs(out[1][0] - out[16][0]) / out[16][0]:.3e}")
+    assert np.array_equal(out[1][1], out["store"][1]) and out[1][0] == out["store"][0] and out[1][2] == out["store"][2]
+    assert np.array_equal(out[1][1], out[16][1])
+    assert abs(out[1][0] - out[16][0]) <= 1e-6 * out[16][0]
 
 
 @pytest.mark.parametrize("N,Nx", [(40, 70), (64, 256)])

@@ -503,6 +503,29 @@ def test_claim_is_dropped_by_a_new_geometry(gpu):
     assert np.array_equal(out[0][1], f.get_volume())
 
 
+def test_a_refused_fgp_end_leaves_the_engine_as_it_was(gpu):
+    """tomo_fgp_end / tomo_fgp_fused_end without a begin are refused (the state error) before they touch the engine: after the cost
+    evaluation of the reconstruction and the refused calls, the SIRT step gives the bits of an engine that never made them."""
+    N, P, Nx = 16, 5, 3
+    ang = np.linspace(-70, 70, P)
+    b = ref64.Matrix(N, ang).fp(S.phantom(Nx, N)).astype(F32)
+    out = []
+    for refused in (True, False):
+        e = S.new_engine("A", nx=Nx, n=N, ang=ang)
+        e.set_tilt_series(b)
+        e.restart_recon()
+        e.SIRT(2)
+        dd = e.data_distance()                                  # the claim: G = A * RECON
+        for call, args in S.REFUSED_WITHOUT_BEGIN.items() if refused else ():
+            with pytest.raises(_lib.TomoError, match="error 3: .*begin has not been called"):      # TOMO_ERR_STATE
+                e.be.c(call, *args)
+        e.SIRT(1)
+        out.append((dd, e.get_volume(), e.data_distance(), e.get_model_projections()))
+    assert out[0][0] > 0 and np.abs(out[0][1]).max() > 0
+    assert np.allclose([out[0][0], out[0][2]], [out[1][0], out[1][2]], rtol=RTOL, atol=0)
+    assert np.array_equal(out[0][1], out[1][1]) and np.array_equal(out[0][3], out[1][3])
+
+
 def _fista_run(writer, reuse):
     e = engine("C")
     e.set_option("fp_reuse", reuse)

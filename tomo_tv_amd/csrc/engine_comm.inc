@@ -166,14 +166,15 @@ int tomo_comm_info(tomo_engine *e, int *world, int *rank)
     return TOMO_OK;
 }
 
-// the field's boundary slices to the ring neighbours' halo planes (before a stencil pass): pack + one group
-int tomo_comm_exchange_halo(tomo_engine *e, int field)
+// the field's boundary slices to the ring neighbours' halo planes h (before a stencil pass): pack + one group
+static int comm_exchange_halo(tomo_engine *e, int field, HaloPair h)
 {
-    NEED_COMM(e);
     int rc;
     if ((rc = tomo_halo_pack_both(e, field, e->comm_send_first, e->comm_send_last))) return rc;
-    return comm_group(e, "halo exchange", [&] { return comm_ring(e, e->comm_send_first, (size_t)e->npix, e->comm_send_last, (size_t)e->npix, e->halo_lo, e->halo_hi); });
+    return comm_group(e, "halo exchange", [&] { return comm_ring(e, e->comm_send_first, (size_t)e->npix, e->comm_send_last, (size_t)e->npix, h.lo, h.hi); });
 }
+
+int tomo_comm_exchange_halo(tomo_engine *e, int field) { NEED_COMM(e); return comm_exchange_halo(e, field, HaloPair{e->halo_lo, e->halo_hi}); }
 
 // all slots of the scalar buffer summed over the ranks into a COPY (the buffer itself keeps this slab's partial sums), read back:
 // blocking form and the snapshot form of tomo_scalars_snapshot (collected by tomo_scalars_snapshot_read)
@@ -211,24 +212,30 @@ int tomo_comm_scalars_snapshot(tomo_engine *e)
 }
 
 // slab-sharded tv_gd, whole call: the halo planes once, then per inner iteration the norm pass, ONE group {all-reduce of sum g^2
-// in place + the gradient's boundary planes round the ring}, the update pass and the halo planes advanced locally
+// + the gradient's boundary planes round the ring}, the update pass and the halo planes advanced locally
 // (engine.py: _tv_descent_one_round is the same protocol over torch.distributed; bit-identical results).  TV before descent
 // stays in TOMO_S_TV as this slab's partial sum; track_vol < 0: plain tv_gd.
-static int comm_tv_gd_impl(tomo_engine *e, int ng, float dPOCS, float eps, int track_vol, int slot)
+// The whole call runs on the ENGINE'S OWN halo planes, whatever the host has bound (the Python classes bind torch tensors for the
+// protocol they drive themselves): the planes are filled by this call's first exchange and advanced inside its update passes, which
+// needs a partner pair to write to (tv_update_impl, tv_folds_halo) -- a caller-bound pair has none.  The planes the engine has in use
+// (halo_lo / halo_hi) are not its business; like every halo plane they are stale until the next exchange, which every TV / FGP call starts with.
+int tomo_comm_tv_gd(tomo_engine *e, int ng, float dPOCS, float eps, int track_vol, int slot)
 {
     NEED_COMM(e);
     int rc;
-    if ((rc = tomo_comm_exchange_halo(e, e->tv_target))) return rc;
+    HaloPair h{e->halo_lo_own, e->halo_hi_own};
+    if ((rc = comm_exchange_halo(e, e->tv_target, h))) return rc;
     if (ng <= 0) {
-        if ((rc = tomo_tv_partial(e, e->tv_target, eps)) || (rc = tomo_positivity(e, e->tv_target))) return rc;
+        if ((rc = tv_value_impl(e, e->tv_target, Halo{h.lo, h.hi}, eps)) || (rc = tomo_positivity(e, e->tv_target))) return rc;
         if (track_vol >= 0) {
             if ((rc = tomo_diff_norm_sq(e, e->tv_target, track_vol, slot))) return rc;
             return tomo_copy_volume(e, track_vol, e->tv_target);
         }
         return TOMO_OK;
     }
+    e->tv_last_eps = eps;
     for (int g = 0; g < ng; ++g) {
-        if ((rc = tomo_tv_grad_planes(e, eps, g == 0, e->comm_send_first, e->comm_send_last))) return rc;
+        if ((rc = tv_grad_impl(e, eps, g == 0, Halo{h.lo, h.hi}, e->comm_send_first, e->comm_send_last))) return rc;
         // the global sum g^2 lands in comm_scal[GNORM]; TOMO_S_GNORM itself keeps this slab's partial sum, so a later
         // tomo_comm_read_scalars (which sums every slot over the ranks) returns the global norm once, not world times
         rc = comm_group(e, "tv_gd round", [&] {
@@ -236,32 +243,12 @@ static int comm_tv_gd_impl(tomo_engine *e, int ng, float dPOCS, float eps, int t
             ncclResult_t r2 = comm_ring(e, e->comm_send_first, (size_t)e->npix, e->comm_send_last, (size_t)e->npix, e->comm_g_lo, e->comm_g_hi);
             return r != ncclSuccess ? r : r2; });
         if (rc) return rc;
-        e->gnorm_override = e->comm_scal + TOMO_S_GNORM;
-        if (g == ng - 1) {
-            rc = track_vol >= 0 ? tomo_tv_update_tracked(e, dPOCS, 1, track_vol, slot) : tomo_tv_update(e, dPOCS, 1);
-        } else {
-            // the update reads the old halo planes, which then follow the neighbours (inside the pass: a second pair of planes)
-            rc = tv_update_impl(e, dPOCS, 0, -1, 0, false, nullptr, nullptr, e->comm_g_lo, e->comm_g_hi);
-        }
-        e->gnorm_override = nullptr;
-        if (rc) return rc;
+        // every update but the last reads the old halo planes, which then follow the neighbours (inside the pass: the partner pair)
+        const bool last = g == ng - 1;
+        if ((rc = tv_update_impl(e, eps, e->comm_scal + TOMO_S_GNORM, h, dPOCS, last, last ? track_vol : -1, slot, false, nullptr, nullptr,
+                                 last ? nullptr : e->comm_g_lo, last ? nullptr : e->comm_g_hi))) return rc;
     }
     return TOMO_OK;
-}
-
-// The whole call runs on the ENGINE'S OWN halo planes, whatever the host has bound (the Python classes bind torch tensors for the
-// protocol they drive themselves): the planes are filled by this call's first exchange and advanced inside its update passes, which
-// needs a second pair to write to (tv_update_impl: "tv_halo_fold") -- a caller-bound pair could not be swapped.  The bound planes come
-// back when the call returns; like every halo plane they are stale until the next exchange, which every TV / FGP call starts with.
-int tomo_comm_tv_gd(tomo_engine *e, int ng, float dPOCS, float eps, int track_vol, int slot)
-{
-    NEED_COMM(e);
-    float *const keep_lo = e->halo_lo, *const keep_hi = e->halo_hi;
-    const bool bound = !(keep_lo == e->halo_lo_own || keep_lo == e->halo_lo_alt);
-    if (bound) { e->halo_lo = e->halo_lo_own; e->halo_hi = e->halo_hi_own; }
-    const int rc = comm_tv_gd_impl(e, ng, dPOCS, eps, track_vol, slot);
-    if (bound) { e->halo_lo = keep_lo; e->halo_hi = keep_hi; }
-    return rc;
 }
 
 // the exchange between two fused FGP iterations: send_last (P1 of my last slice) -> next's lo, send_first (A, P1, P2, P3 of my

@@ -29,7 +29,7 @@ int tomo_get_option(tomo_engine *e, const char *name, int *value)
     if (std::strcmp(name, "create_ms") == 0) { *value = (int)std::min(e->create_ms + 0.5, 2147483647.0); return TOMO_OK; }           // what creating this engine took
     if (std::strcmp(name, "stage_bytes") == 0) { *value = (int)std::min<size_t>(e->stage_bytes, 0x7FFFFFFF); return TOMO_OK; }   // staging buffer of the host data calls (0: never allocated)
     if (std::strcmp(name, "pool_bytes") == 0) { *value = (int)std::min<size_t>(e->pool.bytes(), 0x7FFFFFFF); return TOMO_OK; }   // the registry's live allocations, summed
-    if (std::strcmp(name, "tv_halo_fold") == 0) { *value = e->tv_halo_fold; return TOMO_OK; }
+    if (std::strcmp(name, "tv_halo_fold") == 0) { *value = e->tv.halo_fold; return TOMO_OK; }
     if (std::strcmp(name, "form_fp") == 0) { *value = select_forms(e).fp; return TOMO_OK; }
     if (std::strcmp(name, "form_bp") == 0) { *value = select_forms(e).bp; return TOMO_OK; }
     if (std::strcmp(name, "form_sart") == 0) { *value = select_forms(e).sart; return TOMO_OK; }
@@ -77,12 +77,12 @@ int tomo_set_option(tomo_engine *e, const char *name, int value)
         if (value < 0 || value >= TOMO_S_COUNT) return fail(TOMO_ERR_ARG, "bad scalar slot");
         e->gnorm_slot = value; return TOMO_OK;
     }
-    if (std::strcmp(name, "tv_tz") == 0) { e->tv_tz = value == 4 ? 4 : 8; return TOMO_OK; }
-    if (std::strcmp(name, "tv_halo_fold") == 0) { e->tv_halo_fold = value < 0 ? -1 : (value ? 1 : 0); return TOMO_OK; }
-    if (std::strcmp(name, "tv_march4") == 0) { e->tv_march4 = value ? 1 : 0; return TOMO_OK; }
-    if (std::strcmp(name, "tv_yseg") == 0) { e->tv_yseg = value < 0 ? 0 : value; return TOMO_OK; }
-    if (std::strcmp(name, "tv_recompute") == 0) { e->tv_recompute = value ? 1 : 0; return TOMO_OK; }
-    if (std::strcmp(name, "tv_lds") == 0) { e->tv_lds = value; return TOMO_OK; }   // 1 register march, 8 / 16 LDS march (z-columns per workgroup), 0 direct
+    if (std::strcmp(name, "tv_tz") == 0) { e->tv.tz = value == 4 ? 4 : 8; return TOMO_OK; }
+    if (std::strcmp(name, "tv_halo_fold") == 0) { e->tv.halo_fold = value < 0 ? -1 : (value ? 1 : 0); return TOMO_OK; }
+    if (std::strcmp(name, "tv_march4") == 0) { e->tv.march4 = value ? 1 : 0; return TOMO_OK; }
+    if (std::strcmp(name, "tv_yseg") == 0) { e->tv.yseg = value < 0 ? 0 : value; return TOMO_OK; }
+    if (std::strcmp(name, "tv_recompute") == 0) { e->tv.recompute = value ? 1 : 0; return TOMO_OK; }
+    if (std::strcmp(name, "tv_lds") == 0) { e->tv.lds = value; return TOMO_OK; }   // 1 register march, 8 / 16 LDS march (z-columns per workgroup), 0 direct
     return fail(TOMO_ERR_ARG, std::string("unknown option ") + name);
 }
 

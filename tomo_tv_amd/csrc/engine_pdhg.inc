@@ -60,7 +60,7 @@ static int pdhg_tv_launch(tomo_engine *e, float *x, float **xbar, const float *u
     for (int k = 0; k < 4; ++k) if ((rc = get_scratch(e, &e->pdhg_alt[k], &alt[k]))) return rc;
     if (slot >= 0 && (rc = reduce_begin(e))) return rc;
     PdhgArgs A{x, *xbar, u, *p[0], *p[1], *p[2], alt[0], alt[1], alt[2], alt[3], e->d_colsum_all, precond ? 0.5f : sigma, tau, lambda, theta};
-    const int yseg = tv_rows_per_wave(e, PD_TZ);
+    const int yseg = tv_rows_per_wave(e->tv, tv_shape(e), PD_TZ);
     dim3 grid(tv_march_grid(e->n, PD_TZ, e->sxc / 64, (e->n + yseg - 1) / yseg));
     {
         ProfScope ps(e, TOMO_K_PDHG_TV);

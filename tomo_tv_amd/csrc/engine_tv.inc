@@ -1,7 +1,7 @@
 // engine_tv.inc -- part of tomo_engine.hip (ONE translation unit: the kernels are templates and asm blocks in headers; the host side is
-// split by topic into files that tomo_engine.hip includes in order).  This part: C ABI: TV value / gradient / descent, the sub-slab group's halo calls, FGP (Obj / Grad pair, fused steps, whole-call forms).
-
-// ---- TV -----------------------------------------------------------------------------------------------------------------
+// split by topic into files that tomo_engine.hip includes in order).  This part: C ABI: the halo calls, the sub-slab group's coupling calls, TV value / gradient / update / descent.
+// Which kernel runs is select_tv's answer (tv_form.h).  A pass receives what it uses -- eps, the address of ||g||^2, the halo planes it reads
+// and may replace -- and only the C entries read those from the engine.
 static int field_ptr(tomo_engine *e, int field, float **out)
 {
     if (field == TOMO_FIELD_FGP_D) return get_scratch(e, &e->tvg, out);
@@ -9,12 +9,20 @@ static int field_ptr(tomo_engine *e, int field, float **out)
     return get_vol_ro(e, field, out);   // halo packs and fills only read
 }
 
+struct HaloPair { float *lo, *hi; };       // the plane below slice 0 and the plane above the last slice
+// lo <- the last slice of x, hi <- slice 0: the periodic wrap of a single slab
+static int halo_wrap(tomo_engine *e, const float *x, HaloPair h)
+{
+    hipLaunchKernelGGL(k_halo_wrap, dim3((unsigned)((e->npix + 255) / 256)), dim3(256), 0, e->stream, x, h.lo, h.hi, (int)e->npix, e->sx, e->nx);
+    LAUNCHCHK();
+    return TOMO_OK;
+}
+
 int tomo_bind_halo(tomo_engine *e, void *device_lo, void *device_hi)
 {
     NEED(e);
     HIPCHK(hipStreamSynchronize(e->stream));
-    e->halo_lo = device_lo ? (float *)device_lo : e->halo_lo_own;
-    e->halo_hi = device_hi ? (float *)device_hi : e->halo_hi_own;
+    e->halo_lo = device_lo ? (float *)device_lo : e->halo_lo_own; e->halo_hi = device_hi ? (float *)device_hi : e->halo_hi_own;
     return TOMO_OK;
 }
 
@@ -33,27 +41,20 @@ int tomo_halo_pack_both(tomo_engine *e, int field, void *first_plane, void *last
     NEED(e);
     float *x; int rc; if ((rc = field_ptr(e, field, &x))) return rc;
     if (!first_plane || !last_plane) return fail(TOMO_ERR_ARG, "null destination");
-    // k_halo_wrap(x, lo, hi): lo <- last slice, hi <- slice 0
-    hipLaunchKernelGGL(k_halo_wrap, dim3((unsigned)((e->npix + 255) / 256)), dim3(256), 0, e->stream, x, (float *)last_plane, (float *)first_plane, (int)e->npix, e->sx, e->nx);
-    LAUNCHCHK();
-    return TOMO_OK;
+    return halo_wrap(e, x, HaloPair{(float *)last_plane, (float *)first_plane});
 }
 
 int tomo_halo_local(tomo_engine *e, int field)
 {
     NEED(e);
     float *x; int rc; if ((rc = field_ptr(e, field, &x))) return rc;
-    // below slice 0 sits the last slice, above the last slice sits slice 0
-    hipLaunchKernelGGL(k_halo_wrap, dim3((unsigned)((e->npix + 255) / 256)), dim3(256), 0, e->stream, x, e->halo_lo, e->halo_hi, (int)e->npix, e->sx, e->nx);
-    LAUNCHCHK();
-    return TOMO_OK;
+    return halo_wrap(e, x, HaloPair{e->halo_lo, e->halo_hi});     // below slice 0 sits the last slice, above the last slice sits slice 0
 }
 
 // ---- several slab engines on ONE device (tomo_tv_amd/engine.py: _GroupBackend) ------------------------------------------------
 // A slab can be run as K sub-slabs, each a complete engine with its own allocations and stream: the dependent launch chains of
 // the sub-slabs (a SART sweep is 180 of them) then fill each other's launch gaps and kernel tails.  Slices only couple in the 3-D
 // TV stencils and in the global sums; these three calls are what the coupling needs.
-
 // e's stream waits for everything enqueued on other's stream so far
 int tomo_wait_for(tomo_engine *e, tomo_engine *other)
 {
@@ -103,105 +104,88 @@ int tomo_set_slab_edges(tomo_engine *e, int is_first, int is_last)
     return TOMO_OK;
 }
 
-static int tv_grid(tomo_engine *e)
+// ---- the launchers: one per kernel family (select_tv says which runs) ------------------------------------------------------------
+static TvShape tv_shape(const tomo_engine *e) { return TvShape{e->n, e->nx, e->sxc}; }
+static TvForm tv_form(const tomo_engine *e) { return select_tv(e->tv, tv_shape(e)); }
+static int tv_grid(tomo_engine *e) { return (int)std::min<int64_t>((e->npix * (e->sx / 64) + 3) / 4, 256 * 16); }
+
+// direct-global stencil (reads x twice): the gradient into g, or the value alone (g = null); sums into the main lane's partial sums
+static void launch_tv_direct(tomo_engine *e, const float *x, Halo h, float *g, float eps)
 {
-    int64_t items = e->npix * (e->sx / 64);
-    return (int)std::min<int64_t>((items + 3) / 4, 256 * 16);
+    if (g) hipLaunchKernelGGL(k_tv_grad, dim3(tv_grid(e)), dim3(256), 0, e->stream, x, h, g, e->d_part, eps, e->n, e->nx, e->sx);
+    else hipLaunchKernelGGL(k_tv_value, dim3(tv_grid(e)), dim3(256), 0, e->stream, x, h, e->d_part, eps, e->n, e->nx, e->sx);
+}
+
+// LDS march: the gradient into g (the TV value folded in with 8 columns per workgroup only), or the value alone (g = null)
+static void launch_tv_lds(tomo_engine *e, const TvPass &p, bool with_tv, const float *x, Halo h, float *g, float eps, double *part, double *part_tv)
+{
+    const dim3 grid((unsigned)(((e->n + p.tz - 1) / p.tz) * (e->sxc / 64)), (unsigned)((e->n + p.yseg - 1) / p.yseg));
+    auto lds = [&](auto k) { hipLaunchKernelGGL(k, grid, dim3(256), 0, e->stream, x, h, g, part, eps, e->n, e->nx, e->sx, p.yseg, part_tv); };
+    if (!g) lds(k_tv_grad_lds<8, true, false>);
+    else if (p.family == TV_LDS16) lds(k_tv_grad_lds<16, false>);
+    else with_flag(with_tv, [&](auto W) { lds(k_tv_grad_lds<8, W()>); });
+}
+
+// Register march, every pass of it, one wave per (z block, chunk, y segment): k_tv_march4 where the pass says so, else k_tv_grad_reg.
+// mode: TVM_VALUE the TV value alone (the march without its gradient half: x is read once; k_tv_march4 only without edge lanes);
+// TVM_STORE the gradient into g; TVM_NORM sum g^2 (and TV) only; TVM_UPDATE re-evaluates g and writes up.x_out.
+static void launch_tv_march(tomo_engine *e, const TvPass &p, int mode, bool with_tv, const float *x, Halo h, float *g, float eps, double *part,
+                            double *part_tv, const TvUpd &up)
+{
+    const dim3 grid(tv_march_grid(e->n, p.tz, e->sxc / 64, (e->n + p.yseg - 1) / p.yseg));
+    const bool m4 = p.family == TV_MARCH4;
+    auto march4 = [&](auto k) { hipLaunchKernelGGL(k, grid, dim3(256), 0, e->stream, x, h, part, eps, e->n, e->nx, e->sx, p.yseg, part_tv, up); };
+    auto reg = [&](auto k) { hipLaunchKernelGGL(k, grid, dim3(256), 0, e->stream, x, h, g, part, eps, e->n, e->nx, e->sx, p.yseg, part_tv, up); };
+    if (mode == TVM_VALUE) { if (m4) march4(k_tv_march4<8, true, TVM_VALUE, false>); else reg(k_tv_grad_reg<8, true, false>); }
+    else if (mode == TVM_STORE) with_flag(with_tv, [&](auto W) { reg(k_tv_grad_reg<8, W()>); });
+    else if (mode == TVM_NORM) with_flag(with_tv, [&](auto W) {
+        if (m4) with_flag(p.edge, [&](auto E) { march4(k_tv_march4<8, W(), TVM_NORM, E()>); });
+        else with_int<4, 8>(p.tz, [&](auto TZ) { reg(k_tv_grad_reg<TZ(), W(), true, TVM_NORM>); });
+    });
+    else if (m4) with_flag(p.edge, [&](auto E) { with_flag(up.track != nullptr, [&](auto T) { with_flag(up.stream != 0, [&](auto S) {
+        march4(k_tv_march4<8, false, TVM_UPDATE, E(), T(), S()>);
+    }); }); });
+    else with_int<4, 8>(p.tz, [&](auto TZ) { reg(k_tv_grad_reg<TZ(), false, true, TVM_UPDATE>); });
+}
+
+// ---- value, gradient, update: each receives eps, the address of ||g||^2 and the halo planes it uses; only the C entries read them from the engine
+static int tv_value_impl(tomo_engine *e, int vol, Halo h, float eps)
+{
+    float *x; int rc; if ((rc = get_vol_ro(e, vol, &x))) return rc;
+    const TvPass p = tv_form(e).value;
+    const bool direct = p.family == TV_DIRECT;       // sums into the main lane; the marches into the TV lane
+    if (!direct && !e->d_part_tv && (rc = dev_alloc(e, ENGINE, (void **)&e->d_part_tv, NPART * sizeof(double), true))) return rc;
+    const Lane ln = direct ? main_lane(e) : tv_lane(e);
+    if ((rc = reduce_begin(e, ln))) return rc;
+    if (direct) launch_tv_direct(e, x, h, nullptr, eps);
+    else if (p.family == TV_LDS8) launch_tv_lds(e, p, true, x, h, nullptr, eps, nullptr, e->d_part_tv);
+    else launch_tv_march(e, p, TVM_VALUE, true, x, h, nullptr, eps, nullptr, e->d_part_tv, TvUpd{});
+    LAUNCHCHK();
+    return reduce_end(e, ln, TOMO_S_TV);
 }
 
 // TV of a volume with the halo planes as they are (step form: the caller has exchanged or wrapped them)
-int tomo_tv_partial(tomo_engine *e, int vol, float eps)
-{
-    NEED(e);
-    float *x; int rc; if ((rc = get_vol_ro(e, vol, &x))) return rc;
-    Halo h{e->halo_lo, e->halo_hi};
-    if (e->tv_lds != 8 && e->tv_lds != 1) {   // direct-global stencil (reads x twice)
-        if ((rc = reduce_begin(e))) return rc;
-        hipLaunchKernelGGL(k_tv_value, dim3(tv_grid(e)), dim3(256), 0, e->stream, x, h, e->d_part, eps, e->n, e->nx, e->sx);
-        LAUNCHCHK();
-        return reduce_end(e, TOMO_S_TV);
-    }
-    // the march of the gradient kernels without their gradient half: x is read once
-    if (!e->d_part_tv) { if ((rc = dev_alloc(e, ENGINE, (void **)&e->d_part_tv, NPART * sizeof(double), true))) return rc; }
-    if ((rc = reduce_begin(e, tv_lane(e)))) return rc;
-    const int yseg = 32;
-    if (e->tv_lds == 1 && e->tv_march4 && e->nx % 64 == 0 && e->n % 8 == 0) {
-        // the value alone from the branch-free march (round 3): the R loop without the gradient half
-        hipLaunchKernelGGL((k_tv_march4<8, true, TVM_VALUE, false>), dim3(tv_march_grid(e->n, 8, e->sxc / 64, (e->n + yseg - 1) / yseg)), dim3(256), 0, e->stream, x, h, (double *)nullptr, eps, e->n, e->nx, e->sx, yseg, e->d_part_tv, TvUpd{});
-    } else if (e->tv_lds == 1) {
-        hipLaunchKernelGGL((k_tv_grad_reg<8, true, false>), dim3(tv_march_grid(e->n, 8, e->sxc / 64, (e->n + yseg - 1) / yseg)), dim3(256), 0, e->stream, x, h, (float *)nullptr, (double *)nullptr, eps, e->n, e->nx, e->sx, yseg, e->d_part_tv, TvUpd{});
-    } else {
-        dim3 grid((unsigned)(((e->n + 7) / 8) * (e->sxc / 64)), (unsigned)((e->n + yseg - 1) / yseg));
-        hipLaunchKernelGGL((k_tv_grad_lds<8, true, false>), grid, dim3(256), 0, e->stream, x, h, (float *)nullptr, (double *)nullptr, eps, e->n, e->nx, e->sx, yseg, e->d_part_tv);
-    }
-    LAUNCHCHK();
-    return reduce_end(e, tv_lane(e), TOMO_S_TV);
-}
+int tomo_tv_partial(tomo_engine *e, int vol, float eps) { NEED(e); return tv_value_impl(e, vol, Halo{e->halo_lo, e->halo_hi}, eps); }
 
-// Rows a wave of the register march walks.  32 at a full slab (8 chunks x 64 z-blocks x 16 segments = 8192 waves at 512^3);
-// a thin slab of a multi-GPU run has too few waves at that length (64 slices: 1024 waves, 4 per CU), so the segments
-// shrink until there are ~8 waves per SIMD lane group again -- the 2 halo rows a segment re-reads cost less than the idle CUs.
-static int tv_rows_per_wave(const tomo_engine *e, int tz)
+// sum g^2 into TOMO_S_GNORM (and, with_tv, the TV value into TOMO_S_TV); g itself is stored only by the forms whose update pass reads it.
+// g_first / g_last: the gradient's first and last slice into these buffers as well (the recompute form's norm pass only)
+static int tv_grad_impl(tomo_engine *e, float eps, bool with_tv, Halo h, float *g_first = nullptr, float *g_last = nullptr)
 {
-    if (e->tv_yseg > 0) return e->tv_yseg;
-    const int64_t cols = (int64_t)((e->n + tz - 1) / tz) * (e->sxc / 64);
-    int yseg = 32;
-    while (yseg > TV_YSEG_MIN && cols * ((e->n + yseg - 1) / yseg) < TV_WAVES_WANTED) yseg >>= 1;
-    return yseg;
-}
-
-static int tv_grad_impl(tomo_engine *e, float eps, bool with_tv, float *g_first = nullptr, float *g_last = nullptr)
-{
-    NEED(e);
+    const TvForm f = tv_form(e);
+    if ((g_first || g_last) && !f.planes) return fail(TOMO_ERR_STATE, "gradient planes need the recompute form of the TV march (tv_lds = 1, tv_recompute = 1)");
     float *x, *g; int rc;
-    if ((rc = get_vol(e, e->tv_target, &x))) return rc;
-    if ((rc = get_scratch(e, &e->tvg, &g))) return rc;
-    if ((rc = reduce_begin(e))) return rc;
-    Halo h{e->halo_lo, e->halo_hi};
-    if ((g_first || g_last) && !(e->tv_lds == 1 && e->tv_recompute)) return fail(TOMO_ERR_STATE, "gradient planes need the recompute form of the TV march (tv_lds = 1, tv_recompute = 1)");
-    if (with_tv && e->tv_lds != 8 && e->tv_lds != 1) with_tv = false;
-    if (with_tv) {
-        if (!e->d_part_tv) { if ((rc = dev_alloc(e, ENGINE, (void **)&e->d_part_tv, NPART * sizeof(double), true))) return rc; }
-        if ((rc = reduce_begin(e, tv_lane(e)))) return rc;
-    }
+    if ((rc = get_vol(e, e->tv_target, &x)) || (rc = get_scratch(e, &e->tvg, &g))) return rc;
+    with_tv = with_tv && f.carries_tv;
+    if (with_tv && !e->d_part_tv && (rc = dev_alloc(e, ENGINE, (void **)&e->d_part_tv, NPART * sizeof(double), true))) return rc;
+    if ((rc = reduce_begin(e)) || (with_tv && (rc = reduce_begin(e, tv_lane(e))))) return rc;
     {
         ProfScope ps(e, TOMO_K_TV_GRAD);
-        e->tv_last_eps = eps;
         double *part_tv = with_tv ? e->d_part_tv : nullptr;
-        if (e->tv_lds == 1 && e->tv_recompute) {   // sum g^2 (and TV) only: the update pass re-evaluates g (TVM_UPDATE)
-            TvUpd gp{};
-            gp.wrap_lo = g_last; gp.wrap_hi = g_first;      // g's last / first slice (slab-sharded descent), or null
-            const int tz = e->tv_tz == 4 ? 4 : 8, yseg = tv_rows_per_wave(e, tz);
-            dim3 grid(tv_march_grid(e->n, tz, e->sxc / 64, (e->n + yseg - 1) / yseg));
-            const bool edge = e->nx % 64 != 0 || e->n % 8 != 0;      // lanes without a voxel exist: the march's predicated form
-            with_flag(with_tv, [&](auto W) {
-                if (tz == 8 && e->tv_march4) with_flag(edge, [&](auto E) {
-                    hipLaunchKernelGGL((k_tv_march4<8, W(), TVM_NORM, E()>), grid, dim3(256), 0, e->stream, x, h, e->d_part, eps, e->n, e->nx, e->sx, yseg, part_tv, gp);
-                });
-                else with_int<4, 8>(tz, [&](auto TZ) {
-                    hipLaunchKernelGGL((k_tv_grad_reg<TZ(), W(), true, TVM_NORM>), grid, dim3(256), 0, e->stream, x, h, (float *)nullptr, e->d_part, eps, e->n, e->nx, e->sx, yseg, part_tv, gp);
-                });
-            });
-        } else if (e->tv_lds == 1) {   // register march (k_tv_grad_reg): one wave per (z block, chunk, y segment)
-            int yseg = 32;   // 8 .. 64 rows per wave measured the same; longer segments leave too few waves
-            dim3 grid(tv_march_grid(e->n, 8, e->sxc / 64, (e->n + yseg - 1) / yseg));
-            with_flag(with_tv, [&](auto W) {
-                hipLaunchKernelGGL((k_tv_grad_reg<8, W()>), grid, dim3(256), 0, e->stream, x, h, g, e->d_part, eps, e->n, e->nx, e->sx, yseg, part_tv, TvUpd{});
-            });
-        } else if (e->tv_lds) {
-            int yseg = 32;
-            if (e->tv_lds == 16) {      // (no folded value: with_tv is off)
-                dim3 grid((unsigned)(((e->n + 15) / 16) * (e->sxc / 64)), (unsigned)((e->n + yseg - 1) / yseg));
-                hipLaunchKernelGGL((k_tv_grad_lds<16, false>), grid, dim3(256), 0, e->stream, x, h, g, e->d_part, eps, e->n, e->nx, e->sx, yseg, (double *)nullptr);
-            } else {
-                dim3 grid((unsigned)(((e->n + 7) / 8) * (e->sxc / 64)), (unsigned)((e->n + yseg - 1) / yseg));
-                with_flag(with_tv, [&](auto W) {
-                    hipLaunchKernelGGL((k_tv_grad_lds<8, W()>), grid, dim3(256), 0, e->stream, x, h, g, e->d_part, eps, e->n, e->nx, e->sx, yseg, part_tv);
-                });
-            }
-        } else {
-            hipLaunchKernelGGL(k_tv_grad, dim3(tv_grid(e)), dim3(256), 0, e->stream, x, h, g, e->d_part, eps, e->n, e->nx, e->sx);
-        }
+        TvUpd gp{}; gp.wrap_lo = g_last; gp.wrap_hi = g_first;      // g's last / first slice (slab-sharded descent), or null
+        if (f.recompute) launch_tv_march(e, f.descent, TVM_NORM, with_tv, x, h, nullptr, eps, e->d_part, part_tv, gp);   // the update pass re-evaluates g
+        else if (f.descent.family == TV_REG) launch_tv_march(e, f.descent, TVM_STORE, with_tv, x, h, g, eps, e->d_part, part_tv, gp);
+        else if (f.descent.family == TV_DIRECT) launch_tv_direct(e, x, h, g, eps);
+        else launch_tv_lds(e, f.descent, with_tv, x, h, g, eps, e->d_part, part_tv);
     }
     LAUNCHCHK();
     if (with_tv && (rc = reduce_end(e, tv_lane(e), TOMO_S_TV))) return rc;
@@ -211,393 +195,150 @@ static int tv_grad_impl(tomo_engine *e, float eps, bool with_tv, float *g_first 
 int tomo_tv_set_target(tomo_engine *e, int vol)
 {
     NEED(e);
-    float *x;
-    int rc = get_vol(e, vol, &x);
-    if (rc) return rc;
+    float *x; int rc; if ((rc = get_vol(e, vol, &x))) return rc;
     e->tv_target = vol;
     return TOMO_OK;
 }
 
-int tomo_tv_grad(tomo_engine *e, float eps) { return tv_grad_impl(e, eps, false); }
-int tomo_tv_grad_tv(tomo_engine *e, float eps)
+// The step-form entries.  eps carries from the gradient call to the update call that follows it (the update pass of the recompute form
+// evaluates the gradient again): tv_last_eps, which only they read.
+static int tv_grad_entry(tomo_engine *e, float eps, bool with_tv, float *g_first = nullptr, float *g_last = nullptr)
 {
-    if (e && e->tv_lds != 8 && e->tv_lds != 1) {   // kernels without the folded value: a separate pass
-        int rc = tomo_tv_partial(e, e->tv_target, eps);
-        return rc ? rc : tv_grad_impl(e, eps, false);
-    }
-    return tv_grad_impl(e, eps, true);
+    NEED(e);
+    const int rc = tv_grad_impl(e, eps, with_tv, Halo{e->halo_lo, e->halo_hi}, g_first, g_last);
+    if (!rc) e->tv_last_eps = eps;
+    return rc;
 }
 
-// Slab-sharded descent, one communication round per inner iteration: the norm pass also leaves the gradient's first and last
-// slice in caller buffers (what the neighbours need to advance their halo planes themselves: tomo_tv_halo_apply).
+int tomo_tv_grad(tomo_engine *e, float eps) { return tv_grad_entry(e, eps, false); }
+int tomo_tv_grad_tv(tomo_engine *e, float eps)
+{
+    NEED(e);
+    const bool carries = tv_form(e).carries_tv;      // kernels without the folded value: a separate pass
+    if (!carries) { int rc = tomo_tv_partial(e, e->tv_target, eps); if (rc) return rc; }
+    return tv_grad_entry(e, eps, carries);
+}
+// Slab-sharded descent, one communication round per inner iteration: the norm pass also leaves the gradient's first and last slice in caller
+// buffers (what the neighbours need to advance their halo planes themselves: tomo_tv_halo_apply).
 int tomo_tv_grad_planes(tomo_engine *e, float eps, int with_tv, void *g_first, void *g_last)
 {
-    if (!g_first || !g_last) return fail(TOMO_ERR_ARG, "null plane buffer");
-    return tv_grad_impl(e, eps, with_tv != 0, (float *)g_first, (float *)g_last);
+    return (!g_first || !g_last) ? fail(TOMO_ERR_ARG, "null plane buffer") : tv_grad_entry(e, eps, with_tv != 0, (float *)g_first, (float *)g_last);
 }
 
 // halo planes <- the neighbours' update of those slices: halo - (dPOCS g)/||g|| (clamped), with the received gradient planes
-// g_lo (the lower neighbour's last slice) and g_hi (the upper neighbour's first slice).  Call it AFTER the update pass (which
-// still reads the old planes).
+// g_lo (the lower neighbour's last slice) and g_hi (the upper neighbour's first slice).  Call it AFTER the update pass (which still reads the old planes).
+static int halo_apply(tomo_engine *e, HaloPair h, const float *g_lo, const float *g_hi, const double *gnorm2, float dPOCS, int clamp)
+{
+    hipLaunchKernelGGL(k_halo_apply, dim3((unsigned)((e->npix + 255) / 256)), dim3(256), 0, e->stream, h.lo, h.hi, g_lo, g_hi, gnorm2, dPOCS, clamp, (int)e->npix);
+    LAUNCHCHK();
+    return TOMO_OK;
+}
 int tomo_tv_halo_apply(tomo_engine *e, float dPOCS, int clamp, const void *g_lo, const void *g_hi)
 {
     NEED(e);
     if (!g_lo || !g_hi) return fail(TOMO_ERR_ARG, "null plane buffer");
-    hipLaunchKernelGGL(k_halo_apply, dim3((unsigned)((e->npix + 255) / 256)), dim3(256), 0, e->stream, e->halo_lo, e->halo_hi,
-                       (const float *)g_lo, (const float *)g_hi, gnorm_ptr(e), dPOCS, clamp, (int)e->npix);
-    LAUNCHCHK();
-    return TOMO_OK;
+    return halo_apply(e, HaloPair{e->halo_lo, e->halo_hi}, (const float *)g_lo, (const float *)g_hi, e->d_scal + e->gnorm_slot, dPOCS, clamp);
 }
 
-// the engine's pair of halo planes that is NOT in use (the second pair is allocated on first use): what a pass that still reads the
-// planes in use writes the next ones into
-static int halo_other_pair(tomo_engine *e, float **lo, float **hi)
+// The engine owns two pairs of halo planes (the second is allocated on first use): *out = the partner of the pair h, what a pass that
+// still reads h writes the next planes into.  Planes bound by the caller have no partner.
+static int halo_partner(tomo_engine *e, HaloPair h, HaloPair *out)
 {
     int rc;
-    if (!e->halo_lo_alt) {
-        if ((rc = dev_alloc(e, ENGINE, (void **)&e->halo_lo_alt, e->npix * sizeof(float), true))) return rc;
-        if ((rc = dev_alloc(e, ENGINE, (void **)&e->halo_hi_alt, e->npix * sizeof(float), true))) return rc;
-    }
-    *lo = e->halo_lo == e->halo_lo_own ? e->halo_lo_alt : e->halo_lo_own;
-    *hi = e->halo_hi == e->halo_hi_own ? e->halo_hi_alt : e->halo_hi_own;
+    if (!e->halo_lo_alt && ((rc = dev_alloc(e, ENGINE, (void **)&e->halo_lo_alt, e->npix * sizeof(float), true)) ||
+                            (rc = dev_alloc(e, ENGINE, (void **)&e->halo_hi_alt, e->npix * sizeof(float), true)))) return rc;
+    *out = HaloPair{h.lo == e->halo_lo_own ? e->halo_lo_alt : e->halo_lo_own, h.hi == e->halo_hi_own ? e->halo_hi_alt : e->halo_hi_own};
     return TOMO_OK;
 }
 
-// wrap: also write the new last / first slice into the engine's halo planes (single slab, periodic); plane_last /
-// plane_first: into caller buffers instead (slab-sharded: the planes the ring exchange sends next)
-// hg_lo / hg_hi (slab-sharded descent): the gradient planes received from the ring neighbours; the halo planes are advanced with them
-// (k_halo_apply's expression) -- inside the update pass where it can write a second pair of planes ("tv_halo_fold", the march4 form, the
-// engine's own planes), by a k_halo_apply launch behind it otherwise
-static int tv_update_impl(tomo_engine *e, float dPOCS, int clamp, int track_vol, int slot, bool wrap = false,
+// x <- x - (dPOCS g)/||g|| with ||g||^2 at gnorm2.  halo: the planes the gradient pass read; on return the planes in use.  wrap: the pass also
+// leaves the new last / first slice as the halo planes (single slab, periodic); plane_last / plane_first: in caller buffers instead (the planes
+// the ring exchange sends next).  hg_lo / hg_hi (slab-sharded descent): the gradient planes received from the ring neighbours; the halo planes
+// are advanced with them (k_halo_apply's expression) -- inside the update pass where tv_folds_halo says so, by a k_halo_apply launch behind it
+// otherwise.  The recompute form still reads `halo` while it writes: new planes of the engine's own pair go to its partner, which `halo` names
+// afterwards; planes bound by the caller are refreshed in place by a launch behind the pass.
+static int tv_update_impl(tomo_engine *e, float eps, const double *gnorm2, HaloPair &halo, float dPOCS, int clamp, int track_vol, int slot, bool wrap = false,
                           float *plane_last = nullptr, float *plane_first = nullptr, const float *hg_lo = nullptr, const float *hg_hi = nullptr)
 {
-    NEED(e);
     float *x, *g, *track = nullptr; int rc;
-    if ((rc = get_vol(e, e->tv_target, &x))) return rc;
-    if ((rc = get_scratch(e, &e->tvg, &g))) return rc;
-    if (track_vol >= 0) {
-        if (track_vol == e->tv_target) return fail(TOMO_ERR_ARG, "the tracked volume must differ from the one descended");
-        if (slot < 0 || slot >= TOMO_S_COUNT) return fail(TOMO_ERR_ARG, "bad scalar slot");
-        if ((rc = get_vol(e, track_vol, &track))) return rc;
-        // an evaluation in flight on the second stream may still read the tracked volume (ASD-POCS: the data distance
-        // of the snapshot): order this write behind it on the device; tomo_async_wait later is still valid
-        if ((rc = order_after_async(e))) return rc;
-        if ((rc = reduce_begin(e))) return rc;
-    }
-    if (e->tv_lds == 1 && e->tv_recompute) {
-        // recompute-and-update pass: reads x (+ the halo planes the norm pass used), writes x_new into the second buffer,
-        // which then becomes the volume.  The wrapped planes of x_new go to a second pair of halo buffers (this pass still
-        // reads the old ones), swapped in afterwards; halo buffers bound by the caller are refreshed by a gather launch.
-        float *alt;
-        if ((rc = get_scratch(e, &e->tv_alt, &alt))) return rc;
-        const bool own_halo = e->halo_lo == e->halo_lo_own || e->halo_lo == e->halo_lo_alt;
-        float *wl = plane_last, *wh = plane_first;
-        if (wrap && own_halo && (rc = halo_other_pair(e, &wl, &wh))) return rc;
-        Halo h{e->halo_lo, e->halo_hi};
-        TvUpd up{alt, gnorm_ptr(e), dPOCS, clamp, track, wl, wh, slab_streams(e) ? 1 : 0, nullptr, nullptr, nullptr, nullptr};
-        const bool fold = hg_lo && hg_hi && (e->tv_halo_fold < 0 ? e->sxc >= 128 : e->tv_halo_fold != 0) && own_halo && !wrap && e->tv_tz != 4 && e->tv_march4;
-        if (fold) {
-            up.hg_lo = hg_lo; up.hg_hi = hg_hi;
-            if ((rc = halo_other_pair(e, &up.ho_lo, &up.ho_hi))) return rc;
-        }
-        {
-            ProfScope ps(e, TOMO_K_TV_UPDATE);
-            const int tz = e->tv_tz == 4 ? 4 : 8, yseg = tv_rows_per_wave(e, tz);
-            dim3 grid(tv_march_grid(e->n, tz, e->sxc / 64, (e->n + yseg - 1) / yseg));
-            const bool edge = e->nx % 64 != 0 || e->n % 8 != 0;
-            if (tz == 8 && e->tv_march4) with_flag(edge, [&](auto E) { with_flag(track != nullptr, [&](auto T) { with_flag(up.stream != 0, [&](auto S) {
-                hipLaunchKernelGGL((k_tv_march4<8, false, TVM_UPDATE, E(), T(), S()>), grid, dim3(256), 0, e->stream, x, h, e->d_part, e->tv_last_eps, e->n, e->nx, e->sx, yseg, (double *)nullptr, up);
-            }); }); });
-            else with_int<4, 8>(tz, [&](auto TZ) {
-                hipLaunchKernelGGL((k_tv_grad_reg<TZ(), false, true, TVM_UPDATE>), grid, dim3(256), 0, e->stream, x, h, (float *)nullptr, e->d_part, e->tv_last_eps, e->n, e->nx, e->sx, yseg, (double *)nullptr, up);
-            });
-        }
+    if (track_vol >= 0 && track_vol == e->tv_target) return fail(TOMO_ERR_ARG, "the tracked volume must differ from the one descended");
+    if (track_vol >= 0 && (slot < 0 || slot >= TOMO_S_COUNT)) return fail(TOMO_ERR_ARG, "bad scalar slot");
+    if (track_vol >= TOMO_VOL_SLOTS) return fail(TOMO_ERR_ARG, "bad volume id");
+    if ((rc = get_vol(e, e->tv_target, &x)) || (rc = get_scratch(e, &e->tvg, &g))) return rc;
+    // an evaluation in flight on the second stream may still read the tracked volume (ASD-POCS: the data distance of the snapshot): order this
+    // write behind it on the device; tomo_async_wait later is still valid
+    if (track_vol >= 0 && ((rc = get_vol(e, track_vol, &track)) || (rc = order_after_async(e)) || (rc = reduce_begin(e)))) return rc;
+    const TvForm f = tv_form(e);
+    const bool advance = hg_lo && hg_hi;     // (with both planes or not at all)
+    if (f.recompute) {
+        // recompute-and-update pass: reads x (+ the halo planes the norm pass used), writes x_new into the second buffer, which then becomes the volume
+        float *alt; if ((rc = get_scratch(e, &e->tv_alt, &alt))) return rc;
+        const bool own = halo.lo == e->halo_lo_own || halo.lo == e->halo_lo_alt, fold = advance && tv_folds_halo(f, e->tv, tv_shape(e), own, wrap);
+        HaloPair next{nullptr, nullptr};
+        if (((wrap && own) || fold) && (rc = halo_partner(e, halo, &next))) return rc;
+        TvUpd up{alt, gnorm2, dPOCS, clamp, track, wrap && own ? next.lo : plane_last, wrap && own ? next.hi : plane_first, slab_streams(e) ? 1 : 0, nullptr, nullptr, nullptr, nullptr};
+        if (fold) { up.hg_lo = hg_lo; up.hg_hi = hg_hi; up.ho_lo = next.lo; up.ho_hi = next.hi; }
+        { ProfScope ps(e, TOMO_K_TV_UPDATE); launch_tv_march(e, f.descent, TVM_UPDATE, false, x, Halo{halo.lo, halo.hi}, nullptr, eps, e->d_part, nullptr, up); }
         LAUNCHCHK();
         e->vol[e->tv_target] = alt; e->tv_alt = x;              // the updated volume lives in the partner buffer
-        if (wrap && own_halo) { e->halo_lo = wl; e->halo_hi = wh; }
-        else if (wrap) { if ((rc = tomo_halo_local(e, e->tv_target))) return rc; }
-        if (fold) { e->halo_lo = up.ho_lo; e->halo_hi = up.ho_hi; }
-        else if (hg_lo && hg_hi && (rc = tomo_tv_halo_apply(e, dPOCS, clamp, hg_lo, hg_hi))) return rc;
+        if (next.lo) halo = next;
+        else if (wrap && (rc = halo_wrap(e, alt, halo))) return rc;
+        if (advance && !fold && (rc = halo_apply(e, halo, hg_lo, hg_hi, gnorm2, dPOCS, clamp))) return rc;
         return track ? reduce_end(e, slot) : TOMO_OK;
     }
     int64_t n4 = e->vol_elems() / 4;
     {
         ProfScope ps(e, TOMO_K_TV_UPDATE);
-        float *wl = wrap ? e->halo_lo : plane_last, *wh = wrap ? e->halo_hi : plane_first;
-        double *part = track ? e->d_part : nullptr;
-        with_flag(track != nullptr, [&](auto T) {
-            hipLaunchKernelGGL(k_tv_update<T()>, dim3(grid_1d(n4)), dim3(256), 0, e->stream, (f4 *)x, (const f4 *)g, gnorm_ptr(e), dPOCS, clamp, n4, (f4 *)track, part, wl, wh, e->nx, e->sx / 4);
-        });
+        float *wl = wrap ? halo.lo : plane_last, *wh = wrap ? halo.hi : plane_first;
+        auto update = [&](auto k) { hipLaunchKernelGGL(k, dim3(grid_1d(n4)), dim3(256), 0, e->stream, (f4 *)x, (const f4 *)g, gnorm2, dPOCS, clamp, n4, (f4 *)track, track ? e->d_part : nullptr, wl, wh, e->nx, e->sx / 4); };
+        if (track) update(k_tv_update<true>); else update(k_tv_update<false>);
     }
     LAUNCHCHK();
-    if (hg_lo && hg_hi && (rc = tomo_tv_halo_apply(e, dPOCS, clamp, hg_lo, hg_hi))) return rc;
+    if (advance && (rc = halo_apply(e, halo, hg_lo, hg_hi, gnorm2, dPOCS, clamp))) return rc;
     return track ? reduce_end(e, slot) : TOMO_OK;
 }
 
-int tomo_tv_update(tomo_engine *e, float dPOCS, int clamp) { return tv_update_impl(e, dPOCS, clamp, -1, 0); }
-
+// step form: eps as the last tomo_tv_grad* left it, ||g||^2 from the engine's slot, the engine's planes (which stay: no wrap, no advance)
+static int tv_update_entry(tomo_engine *e, float dPOCS, int clamp, int track_vol, int slot, float *plane_last = nullptr, float *plane_first = nullptr)
+{
+    NEED(e);
+    HaloPair h{e->halo_lo, e->halo_hi};
+    return tv_update_impl(e, e->tv_last_eps, e->d_scal + e->gnorm_slot, h, dPOCS, clamp, track_vol, slot, false, plane_last, plane_first);
+}
+int tomo_tv_update(tomo_engine *e, float dPOCS, int clamp) { return tv_update_entry(e, dPOCS, clamp, -1, 0); }
+int tomo_tv_update_tracked(tomo_engine *e, float dPOCS, int clamp, int track_vol, int slot) { return tv_update_entry(e, dPOCS, clamp, track_vol, slot); }
 int tomo_tv_update_planes(tomo_engine *e, float dPOCS, int clamp, void *first_plane, void *last_plane)
 {
-    if (!first_plane || !last_plane) return fail(TOMO_ERR_ARG, "null plane buffer");
-    return tv_update_impl(e, dPOCS, clamp, -1, 0, false, (float *)last_plane, (float *)first_plane);
+    return (!first_plane || !last_plane) ? fail(TOMO_ERR_ARG, "null plane buffer") : tv_update_entry(e, dPOCS, clamp, -1, 0, (float *)last_plane, (float *)first_plane);
 }
 
-int tomo_tv_update_tracked(tomo_engine *e, float dPOCS, int clamp, int track_vol, int slot)
-{
-    return tv_update_impl(e, dPOCS, clamp, track_vol, slot);
-}
-
-int tomo_fgp_begin(tomo_engine *e) { return tomo_fgp_begin_vol(e, TOMO_VOL_RECON); }
-
-static int fgp_begin_impl(tomo_engine *e, int vol, bool zero_p)
-{
-    NEED(e);
-    float *d, *p; int rc;
-    if ((rc = get_vol(e, vol, &d))) return rc;
-    e->fgp_target = vol;
-    if (zero_p) {   // step form: D and P start as zero fields (tv_fgp.cu:216-227); the fused form needs neither
-        if ((rc = get_scratch(e, &e->tvg, &d))) return rc;
-        HIPCHK(hipMemsetAsync(d, 0, e->vol_elems() * sizeof(float), e->stream));
-    }
-    for (int i = 0; i < 3; ++i) {
-        if ((rc = get_scratch(e, &e->fgp_p[i], &p))) return rc;
-        if (zero_p) HIPCHK(hipMemsetAsync(p, 0, e->vol_elems() * sizeof(float), e->stream));
-    }
-    return TOMO_OK;
-}
-
-int tomo_fgp_begin_vol(tomo_engine *e, int vol) { return fgp_begin_impl(e, vol, true); }
-
-int tomo_fgp_obj(tomo_engine *e, float lambda)
-{
-    NEED(e);
-    if (!e->tvg || !e->fgp_p[2]) return fail(TOMO_ERR_STATE, "tomo_fgp_begin has not been called");
-    ProfScope ps(e, TOMO_K_FGP_OBJ);
-    hipLaunchKernelGGL(k_fgp_obj, dim3(tv_grid(e)), dim3(256), 0, e->stream, e->vol[e->fgp_target], e->tvg, e->fgp_p[0], e->fgp_p[1], e->fgp_p[2], e->halo_lo, e->is_first, lambda, e->n, e->nx, e->sx);
-    LAUNCHCHK();
-    return TOMO_OK;
-}
-
-int tomo_fgp_grad(tomo_engine *e, float lambda)
-{
-    NEED(e);
-    if (!e->tvg || !e->fgp_p[2]) return fail(TOMO_ERR_STATE, "tomo_fgp_begin has not been called");
-    float multip = 1.0f / (26.0f * lambda);
-    ProfScope ps(e, TOMO_K_FGP_GRAD);
-    hipLaunchKernelGGL(k_fgp_grad, dim3(tv_grid(e)), dim3(256), 0, e->stream, e->tvg, e->fgp_p[0], e->fgp_p[1], e->fgp_p[2], e->halo_hi, e->is_last, multip, e->n, e->nx, e->sx);
-    LAUNCHCHK();
-    return TOMO_OK;
-}
-
-int tomo_fgp_end(tomo_engine *e, int iters)
-{
-    if (e) e->claims.prox_landed(e->fgp_target);   // the prox result lands in the volume
-
-    NEED(e);
-    if (!e->tvg) return fail(TOMO_ERR_STATE, "tomo_fgp_begin has not been called");
-    (void)iters;  // D is the zero-filled buffer when no iteration ran, exactly like d_update (tv_fgp.cu:223,272)
-    HIPCHK(hipMemcpyAsync(e->vol[e->fgp_target], e->tvg, e->vol_elems() * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
-    return TOMO_OK;
-}
-
-int tomo_tv(tomo_engine *e, int vol, float eps)
-{
-    int rc;
-    if ((rc = tomo_halo_local(e, vol))) return rc;
-    return tomo_tv_partial(e, vol, eps);
-}
+int tomo_tv(tomo_engine *e, int vol, float eps) { int rc = tomo_halo_local(e, vol); return rc ? rc : tomo_tv_partial(e, vol, eps); }
 
 static int tv_gd_impl(tomo_engine *e, int ng, float dPOCS, float eps, int track_vol, int slot)
 {
-    int rc;
-    if (!e) return fail(TOMO_ERR_ARG, "null engine");
-    // the TV value before descent comes out of the first gradient pass (its denominators are the TV integrand)
-    const bool fold_tv = ng > 0 && (e->tv_lds == 8 || e->tv_lds == 1);
+    NEED(e);
+    int rc;      // the TV value before descent comes out of the first gradient pass (its denominators are the TV integrand)
+    const bool fold_tv = ng > 0 && tv_form(e).carries_tv;
     if (fold_tv) { if ((rc = tomo_halo_local(e, e->tv_target))) return rc; }
     else if ((rc = tomo_tv(e, e->tv_target, eps))) return rc;
+    if (ng > 0) e->tv_last_eps = eps;
     for (int g = 0; g < ng; ++g) {
         // single slab: every descent step but the last also writes the wrapped halo planes of its result
-        if ((rc = tv_grad_impl(e, eps, fold_tv && g == 0))) return rc;
-        if ((rc = tv_update_impl(e, dPOCS, g == ng - 1, g == ng - 1 ? track_vol : -1, slot, g < ng - 1))) return rc;
+        HaloPair h{e->halo_lo, e->halo_hi};
+        if ((rc = tv_grad_impl(e, eps, fold_tv && g == 0, Halo{h.lo, h.hi}))) return rc;
+        rc = tv_update_impl(e, eps, e->d_scal + e->gnorm_slot, h, dPOCS, g == ng - 1, g == ng - 1 ? track_vol : -1, slot, g < ng - 1);
+        e->halo_lo = h.lo; e->halo_hi = h.hi;
+        if (rc) return rc;
     }
     if (ng <= 0) {
         if ((rc = tomo_positivity(e, e->tv_target))) return rc;
-        if (track_vol >= 0) {
-            if ((rc = tomo_diff_norm_sq(e, e->tv_target, track_vol, slot))) return rc;
-            return tomo_copy_volume(e, track_vol, e->tv_target);
-        }
+        if (track_vol >= 0) return (rc = tomo_diff_norm_sq(e, e->tv_target, track_vol, slot)) ? rc : tomo_copy_volume(e, track_vol, e->tv_target);
     }
     return TOMO_OK;
 }
 
 int tomo_tv_gd(tomo_engine *e, int ng, float dPOCS, float eps) { return tv_gd_impl(e, ng, dPOCS, eps, -1, 0); }
-
 int tomo_tv_gd_tracked(tomo_engine *e, int ng, float dPOCS, float eps, int track_vol, int slot)
 {
-    if (track_vol < 0) return fail(TOMO_ERR_ARG, "bad tracked volume");
-    return tv_gd_impl(e, ng, dPOCS, eps, track_vol, slot);
-}
-
-int tomo_tv_fgp(tomo_engine *e, int iters, float lambda) { return tomo_tv_fgp_vol(e, TOMO_VOL_RECON, iters, lambda); }
-
-// ---- fused FGP iteration, step form (single slab and slab-sharded) ------------------------------------------------------
-int tomo_bind_fgp_halo(tomo_engine *e, void *lo, void *hi, void *send_first, void *send_last)
-{
-    NEED(e);
-    if (!lo || !hi || !send_first || !send_last) return fail(TOMO_ERR_ARG, "null plane buffer");
-    HIPCHK(hipStreamSynchronize(e->stream));
-    e->fgp_lo = (float *)lo; e->fgp_hi = (float *)hi; e->fgp_send_first = (float *)send_first; e->fgp_send_last = (float *)send_last;
-    e->fgp_planes2 = false;
-    return TOMO_OK;
-}
-
-// the two-slice-deep set (k_fgp_fused2<.., SHARDED>): lo 5 planes [P1(-1), A(-1), P2(-1), P3(-1), P1(-2)], hi 8 planes
-// [A, P1, P2, P3](nx), [..](nx + 1), send_first 8 planes [A, P1, P2, P3](0), [..](1), send_last 5 planes [P1(nx-1), A(nx-1), P2(nx-1),
-// P3(nx-1), P1(nx-2)].  The one-deep planes of tomo_bind_fgp_halo are the prefixes (1 / 4 / 4 / 1), so both step forms run on it.
-int tomo_bind_fgp_halo2(tomo_engine *e, void *lo, void *hi, void *send_first, void *send_last)
-{
-    int rc = tomo_bind_fgp_halo(e, lo, hi, send_first, send_last);
-    if (rc) return rc;
-    e->fgp_planes2 = true;
-    return TOMO_OK;
-}
-
-// sharded: slab faces that are not global edges read / write the bound planes
-static bool fgp_sharded(const tomo_engine *e) { return !(e->is_first && e->is_last); }
-
-int tomo_fgp_fused_begin(tomo_engine *e, int vol)
-{
-    int rc;
-    if ((rc = fgp_begin_impl(e, vol, false))) return rc;     // the first iteration takes P = 0 as known
-    float *q;
-    for (int i = 0; i < 3; ++i) if ((rc = get_scratch(e, &e->fgp_q[i], &q))) return rc;
-    if (fgp_sharded(e)) {
-        if (!e->fgp_lo) return fail(TOMO_ERR_STATE, "slab-sharded fused FGP needs tomo_bind_fgp_halo");
-        // plane 0 of send_first: the first slice of the prox input (constant over the call)
-        hipLaunchKernelGGL(k_halo_pack, dim3((unsigned)((e->npix + 255) / 256)), dim3(256), 0, e->stream, e->vol[vol], e->fgp_send_first, (int)e->npix, e->sx, 0);
-        LAUNCHCHK();
-        if (e->fgp_planes2 && e->nx >= 2) {      // the deep set: A of slice 1 (send_first plane 4) and of the last slice (send_last plane 1)
-            hipLaunchKernelGGL(k_halo_pack, dim3((unsigned)((e->npix + 255) / 256)), dim3(256), 0, e->stream, e->vol[vol], e->fgp_send_first + 4 * e->npix, (int)e->npix, e->sx, 1);
-            hipLaunchKernelGGL(k_halo_pack, dim3((unsigned)((e->npix + 255) / 256)), dim3(256), 0, e->stream, e->vol[vol], e->fgp_send_last + e->npix, (int)e->npix, e->sx, e->nx - 1);
-            LAUNCHCHK();
-        }
-    }
-    return TOMO_OK;
-}
-
-int tomo_fgp_fused_step(tomo_engine *e, float lambda, int first_iteration)
-{
-    NEED(e);
-    if (!e->fgp_q[2] || !e->fgp_p[2]) return fail(TOMO_ERR_STATE, "tomo_fgp_fused_begin has not been called");
-    const int yseg = 32;
-    const int nzb = (e->n + TVL_TZ - 1) / TVL_TZ, nys = (e->n + yseg - 1) / yseg, nchunk = e->sxc / 64;
-    // one workgroup per item; an XCD-aligned grid when the z blocks split evenly over the 8 XCDs (k_fgp_fused's item map)
-    dim3 grid((nzb & 7) == 0 ? 8u * (unsigned)((nzb >> 3) * nchunk * nys) : (unsigned)(nzb * nchunk * nys));
-    const float multip = 1.0f / (26.0f * lambda);
-    FgpEdge ed{};
-    ed.first = e->is_first; ed.last = e->is_last;
-    if (fgp_sharded(e)) { ed.p1_lo = e->fgp_lo; ed.hi = e->fgp_hi; ed.send_first = e->fgp_send_first; ed.send_last = e->fgp_send_last; }
-    {
-        ProfScope ps(e, TOMO_K_FGP_GRAD);
-        with_flag(fgp_sharded(e), [&](auto SH) {
-            hipLaunchKernelGGL(k_fgp_fused<SH()>, grid, dim3(256), 0, e->stream, e->vol[e->fgp_target], e->fgp_p[0], e->fgp_p[1], e->fgp_p[2],
-                               e->fgp_q[0], e->fgp_q[1], e->fgp_q[2], lambda, multip, e->n, e->nx, e->sx, yseg, first_iteration ? 1 : 0, ed);
-        });
-    }
-    LAUNCHCHK();
-    for (int k = 0; k < 3; ++k) std::swap(e->fgp_p[k], e->fgp_q[k]);
-    return TOMO_OK;
-}
-
-// two iterations in one pass (k_fgp_fused2: P stays on chip between them).  A sharded slab needs the two-slice-deep planes
-// (tomo_bind_fgp_halo2, exchanged once before the call: tomo_comm_fgp_exchange2) and at least two slices on EVERY slab of the ring.
-int tomo_fgp_fused_step2(tomo_engine *e, float lambda, int first_iteration)
-{
-    NEED(e);
-    if (!e->fgp_q[2] || !e->fgp_p[2]) return fail(TOMO_ERR_STATE, "tomo_fgp_fused_begin has not been called");
-    if (fgp_sharded(e) && (!e->fgp_planes2 || !e->fgp_lo)) return fail(TOMO_ERR_STATE, "a sharded tomo_fgp_fused_step2 needs the two-slice-deep planes (tomo_bind_fgp_halo2)");
-    if (fgp_sharded(e) && e->nx < 2) return fail(TOMO_ERR_STATE, "a sharded tomo_fgp_fused_step2 needs at least two slices per slab");
-    const int yseg = 32;                                 // (16 ... 64 within 3 %; 128 and more lose to the tail)
-    const int nzb = (e->n + F2_TZ - 1) / F2_TZ, nys = (e->n + yseg - 1) / yseg, nchunk = (e->nx + F2_SC - 1) / F2_SC;
-    dim3 grid((nzb & 7) == 0 ? 8u * (unsigned)((nzb >> 3) * nchunk * nys) : (unsigned)(nzb * nchunk * nys));
-    const float multip = 1.0f / (26.0f * lambda);
-    {
-        ProfScope ps(e, TOMO_K_FGP_GRAD);
-        const Fgp2Edge ed = fgp_sharded(e) ? Fgp2Edge{e->fgp_lo, e->fgp_hi, e->fgp_send_first, e->fgp_send_last, e->is_first, e->is_last} : Fgp2Edge{};
-        with_flag(fgp_sharded(e), [&](auto SH) {
-            hipLaunchKernelGGL((k_fgp_fused2<false, SH()>), grid, dim3(256), 0, e->stream, e->vol[e->fgp_target], e->fgp_p[0], e->fgp_p[1], e->fgp_p[2],
-                               e->fgp_q[0], e->fgp_q[1], e->fgp_q[2], lambda, multip, e->n, e->nx, e->sx, yseg, first_iteration ? 1 : 0, ed);
-        });
-    }
-    LAUNCHCHK();
-    for (int k = 0; k < 3; ++k) std::swap(e->fgp_p[k], e->fgp_q[k]);
-    return TOMO_OK;
-}
-
-// one more iteration AND the call's result in one pass (k_fgp_fused2<true>): D of the iteration's P, which is never stored; the
-// result is written to a scratch volume that then changes places with the target's buffer.  Whole-volume slabs only.
-int tomo_fgp_fused_last(tomo_engine *e, float lambda, int first_iteration)
-{
-    NEED(e);
-    if (!e->fgp_q[2] || !e->fgp_p[2]) return fail(TOMO_ERR_STATE, "tomo_fgp_fused_begin has not been called");
-    if (fgp_sharded(e)) return fail(TOMO_ERR_STATE, "tomo_fgp_fused_last is for a slab that is the whole volume");
-    if (e->fgp_target < 0 || e->fgp_target >= TOMO_VOL_SLOTS) return fail(TOMO_ERR_STATE, "no target volume");
-    const int yseg = 32;
-    const int nzb = (e->n + F2_TZ - 1) / F2_TZ, nys = (e->n + yseg - 1) / yseg, nchunk = (e->nx + F2_SC - 1) / F2_SC;
-    dim3 grid((nzb & 7) == 0 ? 8u * (unsigned)((nzb >> 3) * nchunk * nys) : (unsigned)(nzb * nchunk * nys));
-    const float multip = 1.0f / (26.0f * lambda);
-    {
-        ProfScope ps(e, TOMO_K_FGP_OBJ);
-        hipLaunchKernelGGL((k_fgp_fused2<true, false>), grid, dim3(256), 0, e->stream, e->vol[e->fgp_target], e->fgp_p[0], e->fgp_p[1], e->fgp_p[2],
-                           e->fgp_q[0], e->fgp_q[1], e->fgp_q[2], lambda, multip, e->n, e->nx, e->sx, yseg, first_iteration ? 1 : 0, Fgp2Edge{});
-    }
-    LAUNCHCHK();
-    std::swap(e->vol[e->fgp_target], e->fgp_q[0]);         // the prox result's buffer becomes the volume; the old one is scratch now
-    e->claims.prox_landed(e->fgp_target);
-    return TOMO_OK;
-}
-
-// the last iteration only needs D (tv_fgp.cu:272), written straight over the target volume
-int tomo_fgp_fused_end(tomo_engine *e, float lambda)
-{
-    if (e) e->claims.prox_landed(e->fgp_target);   // the prox result lands in the volume
-
-    NEED(e);
-    if (!e->fgp_p[2]) return fail(TOMO_ERR_STATE, "tomo_fgp_fused_begin has not been called");
-    ProfScope ps(e, TOMO_K_FGP_OBJ);
-    float *a = e->vol[e->fgp_target];
-    hipLaunchKernelGGL(k_fgp_obj, dim3(tv_grid(e)), dim3(256), 0, e->stream, a, a, e->fgp_p[0], e->fgp_p[1], e->fgp_p[2],
-                       fgp_sharded(e) ? e->fgp_lo : e->halo_lo, e->is_first, lambda, e->n, e->nx, e->sx);
-    LAUNCHCHK();
-    return TOMO_OK;
-}
-
-int tomo_tv_fgp_vol(tomo_engine *e, int vol, int iters, float lambda)
-{
-    int rc;
-    if ((rc = tomo_tv(e, vol, 1e-6f))) return rc;    // tv_fgp.cu:170-189,231-238
-    const bool fused = e && e->fgp_fused && iters > 1;
-    int f = e->is_first, l = e->is_last;
-    e->is_first = e->is_last = 1;
-    if (fused) {
-        // iterations 0..iters-2: one fused kernel each (D stays on chip); the last iteration only needs D
-        rc = tomo_fgp_fused_begin(e, vol);
-        int i = 0;
-        if (e->fgp_pair) for (; i + 2 < iters && !rc; i += 2) rc = tomo_fgp_fused_step2(e, lambda, i == 0);     // pairs, P kept on chip between
-        if (e->fgp_pair && i + 2 == iters) {              // an odd iteration out and the result: one pass
-            if (!rc) rc = tomo_fgp_fused_last(e, lambda, i == 0);
-        } else {
-            for (; i + 1 < iters && !rc; ++i) rc = tomo_fgp_fused_step(e, lambda, i == 0);
-            if (!rc) rc = tomo_fgp_fused_end(e, lambda);
-        }
-        e->is_first = f; e->is_last = l;
-        return rc;
-    }
-    rc = fgp_begin_impl(e, vol, true);
-    for (int i = 0; i < iters && !rc; ++i) {
-        if ((rc = tomo_fgp_obj(e, lambda)) || (rc = tomo_fgp_grad(e, lambda))) break;
-    }
-    e->is_first = f; e->is_last = l;
-    if (rc) return rc;
-    return tomo_fgp_end(e, iters);
+    return track_vol < 0 ? fail(TOMO_ERR_ARG, "bad tracked volume") : tv_gd_impl(e, ng, dPOCS, eps, track_vol, slot);
 }

@@ -399,13 +399,7 @@ __global__ __launch_bounds__(256) void k_tv_grad_lds(const float *__restrict__ x
 // What did help a little: evaluating R at the phantom slice once per row for all columns on PACKED inputs (lane j = column j,
 // two gather loads per row) instead of once per column on the edge registers: -72 vector instructions per row, an inner
 // iteration 516 -> 500 us at 512 slices, 93 -> 90.5 us at 64 (same box, both libraries side by side).
-// workgroups (4 waves) of the march kernels' item space, for the XCD-aware map above
-inline unsigned tv_march_grid(int n, int tz, int nchunk, int nys)
-{
-    const int nzb = (n + tz - 1) / tz;
-    if ((nzb & 7) == 0) return 8u * (unsigned)(((int64_t)(nzb >> 3) * nchunk * nys + 3) / 4);
-    return (unsigned)(((int64_t)nzb * nchunk * nys + 3) / 4);
-}
+// (The grid of the march kernels' item space: tv_march_grid, tv_form.h.)
 
 // MODE (round 2).  HBM WRITES are the scarce resource on this part (a 537 MB memset runs at 3.0 TB/s, a read stream at ~6;
 // tools/whatif_sart.py), and a tv_gd inner iteration as "gradient pass (write g) + update pass (read x, g; write x)" writes the

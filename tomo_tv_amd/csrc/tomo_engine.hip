@@ -12,6 +12,7 @@
 #include "dev_pool.h"
 #include "claims.h"
 #include "sart_host.h"
+#include "tv_form.h"
 
 #include <dlfcn.h>
 #if __has_include(<rccl/rccl.h>)
@@ -149,23 +150,22 @@ struct tomo_engine {
     uint2 *d_went = nullptr;
     float lipschitz = 0.f, lipschitz_cimmino = 0.f;
     int sart_fused = 1;                      // 1: SART sweep as a chain of fused BP+FP steps; 0: separate FP and BP per angle
-    int tv_lds = 1, fp_all_lpr = 16;
-    // tv_recompute: a tv_gd inner iteration as "norm pass (no store) + recompute-and-update pass into a second buffer" instead
+    int fp_all_lpr = 16;
+    // The six "tv_*" switches, read by select_tv / tv_folds_halo (tv_form.h) and the option calls only.
+    // recompute: a tv_gd inner iteration as "norm pass (no store) + recompute-and-update pass into a second buffer" instead
     // of "gradient pass (store g) + update pass": one volume write instead of two (HBM writes are the scarce resource)
-    int tv_recompute = 1, tv_tz = 8;              // tv_tz: z-columns per wave of the register march (8 or 4)
-    int tv_yseg = 0;                              // rows per wave of the register march; 0 = by slab size (tv_rows_per_wave)
-    int tv_march4 = 1;                            // norm / update passes by k_tv_march4 (no row rotation) instead of k_tv_grad_reg
-    // slab-sharded descent: the update pass advances the halo planes itself (lanes 1..8 of the packed edge registers: one 32-byte load of
+    // tz: z-columns per wave of the register march (8 or 4); yseg: its rows per wave, 0 = by slab size (tv_rows_per_wave);
+    // march4: norm / update passes by k_tv_march4 (no row rotation) instead of k_tv_grad_reg
+    // halo_fold (slab-sharded descent): the update pass advances the halo planes itself (lanes 1..8 of the packed edge registers: one 32-byte load of
     // the received gradient plane and one store per row and plane) instead of a k_halo_apply launch per inner iteration.  -1 = automatic:
     // where the slab has two chunks or more.  Measured (round 6, bench.py --force-dist, world-1 RCCL group): 128 slices 3.53 against 3.62 ms
     // per step; 64 slices (ONE chunk: every wave of the pass holds both planes) 2.04 against 2.01 -- so a one-chunk slab keeps the launch.
     // (The first form, one lane looping over the row's eight pixels: 2.165 against 2.012 at 64 slices.)  1 / 0 force it.
-    int tv_halo_fold = -1;
+    TvOptions tv;
     int gnorm_slot = TOMO_S_GNORM;                // scalar slot the TV update takes ||g||^2 from (slab groups: TOMO_S_GNORM_ALL)
-    double *gnorm_override = nullptr;             // tomo_comm_tv_gd: the all-reduced sum g^2 (the slot itself keeps the slab's partial sum)
     hipEvent_t ev_peer = nullptr;                 // tomo_wait_for: "everything enqueued on this engine so far"
     hipEvent_t ev_io = nullptr;                   // tomo_set_*_device / tomo_get_*_device: orders the caller's stream and the engine's
-    float tv_last_eps = 1e-6f;
+    float tv_last_eps = 1e-6f;                    // step form: eps of the last tomo_tv_grad*, which the tomo_tv_update* that follows passes on
     float *tv_alt = nullptr, *halo_lo_alt = nullptr, *halo_hi_alt = nullptr;
     // fp_all_lpr: all-angle FP: lanes per ray of the narrow-chunk form (0 = wide form)
     SegItemD *d_seg_exec = nullptr;
@@ -328,11 +328,9 @@ struct tomo_engine {
     size_t vol_elems() const { return (size_t)npix * sx; }
     size_t sino_elems() const { return (size_t)nrows * sx; }
     // every device allocation of the engine (dev_pool.h).  Caller-bound buffers and the aliases of owned ones (d_scal, halo_lo / halo_hi,
-    // fgp_lo ..., pdhg_lo ..., gnorm_override) are never registered.
+    // fgp_lo ..., pdhg_lo ...) are never registered.
     DevPool pool{pool_alloc, pool_free};
 };
-
-static inline double *gnorm_ptr(const tomo_engine *e) { return e->gnorm_override ? e->gnorm_override : e->d_scal + e->gnorm_slot; }
 
 constexpr DevPool::Life GEOMETRY = DevPool::GEOMETRY, COMM = DevPool::COMM, ENGINE = DevPool::ENGINE;
 // *p = a new device buffer of the engine, owned by its pool; zero: cleared on the engine's stream
@@ -497,8 +495,6 @@ static int reduce_end(tomo_engine *e, const Lane &ln, int slot)
 static int reduce_begin(tomo_engine *e) { return reduce_begin(e, main_lane(e)); }
 static int reduce_end(tomo_engine *e, int slot) { return reduce_end(e, main_lane(e), slot); }
 
-constexpr int TV_YSEG_MIN = 8, TV_WAVES_WANTED = 4096;   // round 3: the march holds 4 waves per SIMD = 4096 resident waves: one full round
-                                                         // (8192 before; 128 slices: 16 rows per wave 94.5 us per inner iteration against 8 rows ~100)
 static int grid_1d(int64_t n4) { int64_t b = (n4 + 255) / 256; return (int)std::min<int64_t>(std::max<int64_t>(b, 1), 4096); }
 
 #include "engine_launch.inc"
@@ -509,6 +505,7 @@ extern "C" {
 
 #include "engine_api.inc"
 #include "engine_tv.inc"
+#include "engine_fgp.inc"
 #include "engine_pdhg.inc"
 #include "engine_align.inc"
 #include "engine_tilt.inc"
