@@ -268,6 +268,36 @@ int tomo_sino_axis_profile(tomo_engine *e, int sino, double *out_host);         
 int tomo_volume_rot_derivative(tomo_engine *e, int src_vol, int dst_vol);
 int tomo_sino_tilt_normal(tomo_engine *e, int b_sino, int g_sino, int d_sino, int margin, double *out_host /* [Nproj][4] */);  /* waits */
 
+/* ---- conditioning of the tilt series (kernels_condition.hip.h; the drivers are TomoGPU.subtract_background / despeckle /
+ * normalize_intensity / condition) -------------------------------------------------------------------------------------------
+ * The reference cleans every measured image on the host before it centres it (cpu/utils/logger.py:93): background_subtract
+ * (cpu/utils/logger.py:255-263) removes the mean of the image's first-quarter corner.  These three calls do that on the resident series
+ * and add the two steps electron tomography takes for granted, outlier ("hot pixel", X-ray) removal by a local median and a gain
+ * per projection.  Conventions of the alignment block: projection a of a slot is the image X_a[r][s], 0 <= r < Nray, 0 <= s < Nslice;
+ * padding slices are never read as data and stay zero in whatever is written.  One whole-volume engine only: TOMO_ERR_STATE on an
+ * engine with a communicator, a slab of a larger volume (tomo_set_slab_edges) or released geometry.  A refused call enqueues nothing and
+ * writes nothing.  Source slots are only read (no claim on TOMO_SINO_G is dropped unless G is the destination).
+ *   tomo_sino_window_stats: out_host[a] = {sum X, sum X^2, min X, max X} over r0 <= r < r1, s0 <= s < s1 of projection a.  The sums
+ *       in binary64 from the first sample, the square a binary64 product of the converted sample; two fixed-order reduction stages,
+ *       no atomics: the same bits from call to call.  The mean of the window [0, Nray / 4) x [0, Nslice / 4) is the background of
+ *       cpu/utils/logger.py:255-263.  Waits for its result.  TOMO_ERR_ARG: an empty window or one that leaves the image.
+ *   tomo_sino_median: m = the median of the (2 radius + 1)^2 samples around (r, s) of projection a of src, radius 1 or 2 (the 5th
+ *       smallest of 9, the 13th smallest of 25), indices clamped to the image: the border is replicated, projections never mix.  A
+ *       selection, never an average: m is one of the samples (among tied zeros the sign is unspecified).  d = x - m, one binary32
+ *       subtraction.  out_host[a] = {sum d, sum |d|, sum d^2, the number of samples, the number replaced} in binary64, summed like
+ *       the window statistics.  thresh_host == NULL only measures: nothing is written, dst must be -1, the number replaced is 0.
+ *       Otherwise dst = (|d| > thresh_host[a]) ? m : x, compared in binary32, src != dst: +Inf copies the source bits, 0 gives the
+ *       median image.  Inputs are taken as finite: a NaN makes the values of the windows it lies in unspecified and nothing else.
+ *       Waits for its result.  TOMO_ERR_ARG: radius not 1 or 2, a negative or NaN threshold, src == dst, dst != -1 when measuring.
+ *   tomo_sino_intensity: dst = fma(gain_a, x, offset_a), one fused operation, gain_offset_host[a] = {gain_a, offset_a}; with
+ *       clamp != 0 followed by max(0, .) (a NaN or -0 gives +0).  src == dst is allowed; gain 1 with offset 0 copies.  Enqueued on the
+ *       engine's stream, no wait (the table is consumed before the call returns).  TOMO_ERR_ARG: a non-finite gain or offset.
+ * TOMO_ERR_ARG also: a bad slot, a null pointer. */
+int tomo_sino_window_stats(tomo_engine *e, int sino, int r0, int r1, int s0, int s1, double *out_host /* [Nproj][4] */);   /* waits; logger.py:255-263 */
+int tomo_sino_median(tomo_engine *e, int src, int dst, int radius, const float *thresh_host /* [Nproj] or NULL */,
+                     double *out_host /* [Nproj][5] */);                                     /* waits */
+int tomo_sino_intensity(tomo_engine *e, int src, int dst, const float *gain_offset_host /* [Nproj][2] */, int clamp);   /* logger.py:261 */
+
 /* ---- binning and prolongation between two engines (coarse-to-fine drivers) --------------------------------------------------
  * `fine` and `coarse` are two different whole-volume engines on one device whose grids differ by factor = f, 2 or 4:
  *     fine Nray == f * coarse Nray,   coarse Nslice == ceil(fine Nslice / f),   and for tomo_sino_bin the same Nproj.

@@ -128,6 +128,9 @@ SIGNATURES = {
     "tomo_sino_axis_profile": [_p, _i, _p],
     "tomo_volume_rot_derivative": [_p, _i, _i],
     "tomo_sino_tilt_normal": [_p, _i, _i, _i, _i, _p],
+    "tomo_sino_window_stats": [_p, _i, _i, _i, _i, _i, _p],
+    "tomo_sino_median": [_p, _i, _i, _i, _p, _p],
+    "tomo_sino_intensity": [_p, _i, _i, _p, _i],
     "tomo_sino_bin": [_p, _i, _p, _i, _i],
     "tomo_volume_bin": [_p, _i, _p, _i, _i],
     "tomo_volume_prolong": [_p, _i, _p, _i, _i],

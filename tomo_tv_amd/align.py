@@ -460,3 +460,32 @@ def center_of_mass_shifts(moments, nray, nslice):
         out[a, 0] = -(int(m[a, 1] / m[a, 0]) - nray // 2)
         out[a, 1] = -(int(m[a, 2] / m[a, 0]) - nslice // 2)
     return out
+
+
+# ---- conditioning of the tilt series: the host side of ``tomoengine.sino_window_stats`` / ``sino_median`` / ``sino_intensity`` --------
+def background_window(Nray, Nslice):
+    """The reference's background window (cpu/utils/logger.py:258-259: the first quarter of both axes) as ``(r0, r1, s0, s1)``:
+    rays [0, Nray // 4), slices [0, Nslice // 4), each at least 1 wide (the reference's window is empty below 4 samples)."""
+    return 0, max(1, int(Nray) // 4), 0, max(1, int(Nslice) // 4)
+
+
+def despeckle_thresholds(stats, n_sigma):
+    """(Nproj,) float32 thresholds from the (Nproj, 5) sums of a measuring ``sino_median``: ``n_sigma * sqrt(pi / 2) * (sum |d| / n)``,
+    the Gaussian sigma estimated from the mean absolute deviation from the local median -- which the outliers themselves inflate far
+    less than they inflate the RMS.  A projection whose mean absolute deviation is 0 gets ``+Inf``: nothing is replaced there."""
+    st = np.asarray(stats, np.float64)
+    if not float(n_sigma) > 0:
+        raise ValueError("n_sigma must be positive")
+    mad = st[:, 1] / st[:, 3]
+    with np.errstate(over="ignore"):
+        return np.where(mad > 0, float(n_sigma) * np.sqrt(np.pi / 2) * mad, np.inf).astype(np.float32)
+
+
+def mass_gains(moments):
+    """(Nproj,) float64 gains ``mean_a(mass) / mass_a`` from the (Nproj, >= 1) sums of ``sino_moments`` or ``sino_window_stats``
+    (column 0: the total mass): for a parallel-beam series the mass is the same in every projection.  ``ValueError`` if a mass is
+    not positive (subtract the background first, and mind what it leaves of an empty projection)."""
+    mass = np.asarray(moments, np.float64).reshape(len(moments), -1)[:, 0]
+    if not np.all(mass > 0) or not np.all(np.isfinite(mass)):
+        raise ValueError("every projection needs a positive, finite total mass")
+    return mass.mean() / mass

@@ -289,6 +289,7 @@ struct tomo_engine {
     double *al_part = nullptr, *al_mom = nullptr, *al_out = nullptr;
     float *al_mean = nullptr;
     size_t al_part_bytes = 0, al_out_bytes = 0;
+    std::vector<float> cond_tab;                  // conditioning (engine_condition.inc): the host copy of the last {gain, offset} table enqueued
     // DART (engine_dart.inc): one state byte per voxel, the number of thresholds it was made with (-1: no segmentation yet), and the
     // class statistics' partial sums [DART_STATS_BLOCKS + 1][16][2] (the last row: the result)
     uint8_t *dart_state = nullptr;
@@ -509,6 +510,7 @@ extern "C" {
 #include "engine_pdhg.inc"
 #include "engine_align.inc"
 #include "engine_tilt.inc"
+#include "engine_condition.inc"
 #include "engine_bin.inc"
 #include "engine_dual.inc"
 #include "engine_affine3d.inc"

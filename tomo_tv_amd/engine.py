@@ -428,6 +428,7 @@ class _GroupBackend:
     c_sino_bin = c_volume_bin = c_volume_prolong = c_volume_cross = c_volume_cross_axpy = _no_align
     c_volume_affine = c_volume_affine_axpy = c_volume_affine_normal = _no_align
     c_volume_rot_derivative = c_sino_tilt_normal = _no_align
+    c_sino_window_stats = c_sino_median = c_sino_intensity = _no_align
 
     def c_set_tilt_series(self, ptr):
         self._rows("set_sinogram", SINO_B, ptr, self.nray * self.nproj * 4)
@@ -1102,6 +1103,47 @@ class _EngineBase:
         if sh.shape != (self.Nproj, 2):
             raise ValueError(f"shifts must have shape {(self.Nproj, 2)}, got {sh.shape}")
         self.be.c("sino_shift", int(src), int(dst), _ptr(sh), int(bool(wrap)))
+
+    # ---- conditioning of the tilt series (include/tomo_hip.h: tomo_sino_window_stats / tomo_sino_median / tomo_sino_intensity; the
+    # host rules are in align.py, the drivers on TomoGPU) ------------------------------------------------------------------------
+    def sino_window_stats(self, sino=SINO_B, window=None):
+        """(Nproj, 4) float64: sum X, sum X^2, min X, max X of every projection of sinogram slot ``sino`` over the window
+        ``(r0, r1, s0, s1)`` = rays r0 <= r < r1, slices s0 <= s < s1 (``None``: the whole image).  The sums are binary64 from the
+        first sample; the same bits from call to call.  ``align.background_window`` gives the corner whose mean the reference
+        subtracts (cpu/utils/logger.py:255-263)."""
+        self._align_one_engine()
+        r0, r1, s0, s1 = (0, self.Ny, 0, self.Nslice_) if window is None else (int(v) for v in window)
+        out = np.empty((self.Nproj, 4), np.float64)
+        self.be.c("sino_window_stats", int(sino), r0, r1, s0, s1, _ptr(out))
+        return out
+
+    def sino_median(self, src, dst=None, radius=1, thresh=None):
+        """(Nproj, 5) float64 per projection of sinogram slot ``src``: sum d, sum |d|, sum d^2, the number of samples and the number
+        replaced, with d = x - m and m the median of the (2 ``radius`` + 1)^2 samples around x (``radius`` 1 or 2; the border is
+        replicated).  ``thresh=None`` only measures (``dst`` must be ``None``).  Otherwise ``thresh`` = (Nproj,) float32 (or one
+        value for all) and slot ``dst`` != ``src`` receives ``m`` where ``|d| > thresh`` and ``x`` elsewhere
+        (``align.despeckle_thresholds`` makes thresholds from a measuring call)."""
+        self._align_one_engine()
+        out = np.empty((self.Nproj, 5), np.float64)
+        if thresh is None:
+            if dst is not None:
+                raise ValueError("a measuring call (thresh=None) writes nothing: dst must be None")
+            self.be.c("sino_median", int(src), -1, int(radius), None, _ptr(out))
+            return out
+        if dst is None:
+            raise ValueError("a replacing call needs a destination slot")
+        th = np.ascontiguousarray(np.broadcast_to(np.asarray(thresh, np.float32), (self.Nproj,)))
+        self.be.c("sino_median", int(src), int(dst), int(radius), _ptr(th), _ptr(out))
+        return out
+
+    def sino_intensity(self, src, dst, gain, offset, clamp=False):
+        """dst_p = fma(gain_p, src_p, offset_p) in binary32, one fused operation, then with ``clamp`` max(0, .); ``gain`` and
+        ``offset`` are scalars or (Nproj,).  ``src`` == ``dst`` is allowed; gain 1 with offset 0 copies a slot.  Enqueued, no wait."""
+        self._align_one_engine()
+        tab = np.empty((self.Nproj, 2), np.float32)
+        tab[:, 0] = np.broadcast_to(np.asarray(gain, np.float32), (self.Nproj,))
+        tab[:, 1] = np.broadcast_to(np.asarray(offset, np.float32), (self.Nproj,))
+        self.be.c("sino_intensity", int(src), int(dst), _ptr(tab), int(bool(clamp)))
 
     def sino_affine(self, src, dst, matrices):
         """dst_p[r][s] = src_p(r', s'), bilinear, zeros outside the image, with r' = m00 r + m01 s + m02, s' = m10 r + m11 s + m12 and

@@ -123,6 +123,7 @@ class TomoGPU:
         self.recon = None
         self._align_kept, self._align_shifts, self._align_rot = False, None, None      # a new series: nothing kept, nothing applied
         self._pyramid = {}                                                             # ... and no binned copy of the old one
+        self._align_wrap, self._conditioning = False, None                             # ... and nothing done to its intensities
         t = _device_tensor(tiltSeries)
         if t is None:
             self.tomo.set_tilt_series(pytvlib.pack_tilt_series(tiltSeries))
@@ -390,12 +391,16 @@ class TomoGPU:
         stored = getattr(self, "_align_rot", None)
         if stored is None and rotation_deg is None:
             t.sino_shift(self.ALIGN_SLOT, dst, shifts, wrap=wrap)
+            if dst == SINO_B:
+                self._align_wrap = bool(wrap)          # what the conditioning drivers re-apply (_conditioned)
             return
         if wrap:
             raise ValueError("wrap=True cannot be combined with a rotation or magnification: the affine pass has no wrap form")
         rot, mag = stored if stored is not None else (0.0, 1.0)
         sh = np.asarray(shifts, np.float32).astype(np.float64)
         t.sino_affine(self.ALIGN_SLOT, dst, align.affine_matrices(sh, rot if rotation_deg is None else rotation_deg, mag, self.Nray, self.Nslice))
+        if dst == SINO_B:
+            self._align_wrap = False
 
     def set_alignment(self, shifts, wrap=False, *, rotation_deg=None, magnification=None):
         """Apply total shifts to the series as it was given (not on top of earlier ones): projection a moves by (dr, ds) =
@@ -471,6 +476,95 @@ class TomoGPU:
         shifts = align.center_of_mass_shifts(t.sino_moments(self.ALIGN_SLOT), self.Nray, self.Nslice)
         self.set_alignment(shifts, wrap=True)
         return shifts
+
+    # ---- conditioning of the series as given (an extension of cpu/utils/logger.py:93, which subtracts a background on the host before
+    # it centres; include/tomo_hip.h: tomo_sino_window_stats / tomo_sino_median / tomo_sino_intensity; the rules are in align.py) ----
+    @property
+    def conditioning(self):
+        """What the conditioning drivers have done to the series since ``set_tilt_series``, per projection: ``gain`` and ``offset``
+        (the series as given went through ``gain * x + offset`` in total, outlier replacement aside) and ``replaced``, the number
+        of samples ``despeckle`` replaced."""
+        c = getattr(self, "_conditioning", None)
+        if c is None:
+            c = self._conditioning = dict(gain=np.ones(self.Nangles), offset=np.zeros(self.Nangles), replaced=np.zeros(self.Nangles, np.int64))
+        return {k: v.copy() for k, v in c.items()}
+
+    def _conditioned(self, t):
+        """The series as given (``ALIGN_SLOT``) has changed: resample it again by the alignment in force (the shifts, the stored
+        rotation and magnification, the ``wrap`` last used), and drop what was derived from the old series."""
+        self._align_resample(t, self.get_alignment(), wrap=getattr(self, "_align_wrap", False))
+        self._pyramid = {}
+        self.recon = None
+
+    def _apply_intensity(self, t, gain, offset, clamp=False):
+        t.sino_intensity(self.ALIGN_SLOT, self.ALIGN_SLOT, gain, offset, clamp=clamp)
+        self.conditioning                                # (creates the record)
+        c = self._conditioning
+        c["offset"] = np.asarray(gain, np.float64) * c["offset"] + np.asarray(offset, np.float64)
+        c["gain"] = np.asarray(gain, np.float64) * c["gain"]
+        self._conditioned(t)
+
+    def subtract_background(self, window=None, clamp=False):
+        """Subtract from every projection of the series as given the mean of its samples in ``window`` = ``(r0, r1, s0, s1)``, rays
+        r0 <= r < r1 and slices s0 <= s < s1; ``None`` is the reference's first-quarter corner (cpu/utils/logger.py:255-263,
+        ``align.background_window``).  With ``clamp`` negative results become 0.  An outlier inside the window enters its mean.  The current alignment is re-applied.  Returns the
+        (Nangles,) backgrounds removed (the offset applied is their binary32 rounding, negated)."""
+        t = self._align_engine()
+        r0, r1, s0, s1 = align.background_window(self.Nray, self.Nslice) if window is None else (int(v) for v in window)
+        st = t.sino_window_stats(self.ALIGN_SLOT, (r0, r1, s0, s1))
+        mean = st[:, 0] / float((r1 - r0) * (s1 - s0))
+        offset = -mean.astype(np.float32)
+        self._apply_intensity(t, np.ones(self.Nangles, np.float32), offset, clamp=clamp)
+        return -offset.astype(np.float64)
+
+    def despeckle(self, n_sigma=6.0, radius=1, passes=1):
+        """Replace outliers ("hot pixels", X-ray hits) of the series as given by the median of their (2 ``radius`` + 1)^2
+        neighbourhood: per pass one measuring ``sino_median``, the thresholds ``align.despeckle_thresholds(stats, n_sigma)`` (per
+        projection ``n_sigma`` Gaussian sigmas, estimated from the mean absolute deviation from the local median), one replacing call
+        into ``ALIGN_SCRATCH_SLOT`` and a move back.  The current alignment is re-applied.  Returns the (Nangles,) int64 numbers of
+        samples replaced, summed over the passes."""
+        if int(passes) < 1:
+            raise ValueError("passes must be at least 1")
+        t = self._align_engine()
+        total = np.zeros(self.Nangles, np.int64)
+        for _ in range(int(passes)):
+            th = align.despeckle_thresholds(t.sino_median(self.ALIGN_SLOT, radius=radius), n_sigma)
+            st = t.sino_median(self.ALIGN_SLOT, self.ALIGN_SCRATCH_SLOT, radius=radius, thresh=th)
+            t.sino_intensity(self.ALIGN_SCRATCH_SLOT, self.ALIGN_SLOT, 1.0, 0.0)
+            total += st[:, 4].astype(np.int64)
+        self.conditioning
+        self._conditioning["replaced"] = self._conditioning["replaced"] + total
+        self._conditioned(t)
+        return total
+
+    def normalize_intensity(self, mode="mass"):
+        """Scale every projection of the series as given so that all have the same total mass, the mean of the masses before
+        (``align.mass_gains``: a parallel-beam projection of one object has the same mass at every tilt).  ``"mass"`` is the only
+        mode.  The current alignment is re-applied.  Returns the (Nangles,) gains applied (binary32 values)."""
+        if mode != "mass":
+            raise ValueError(f"unknown mode {mode!r}: 'mass' is the only one")
+        t = self._align_engine()
+        gain = align.mass_gains(t.sino_moments(self.ALIGN_SLOT)).astype(np.float32)
+        self._apply_intensity(t, gain, np.zeros(self.Nangles, np.float32))
+        return gain.astype(np.float64)
+
+    def condition(self, background=True, despeckle=True, normalize=True, **kw):
+        """``subtract_background``, ``despeckle`` and ``normalize_intensity`` in that order (the reference's step first, then the two
+        it lacks), each unless switched off; the keywords ``window`` and ``clamp`` go to the first, ``n_sigma``, ``radius`` and
+        ``passes`` to the second, ``mode`` to the third.  Returns ``{"background": ..., "replaced": ..., "gain": ...}`` with what each
+        step that ran returned."""
+        known = {"window", "clamp", "n_sigma", "radius", "passes", "mode"}
+        if set(kw) - known:
+            raise TypeError(f"unknown keyword(s) {sorted(set(kw) - known)}")
+        pick = lambda *names: {k: kw[k] for k in names if k in kw}  # noqa: E731
+        out = {}
+        if background:
+            out["background"] = self.subtract_background(**pick("window", "clamp"))
+        if despeckle:
+            out["replaced"] = self.despeckle(**pick("n_sigma", "radius", "passes"))
+        if normalize:
+            out["gain"] = self.normalize_intensity(**pick("mode"))
+        return out
 
     def _model_leave_one_out(self, niter):
         """Into sinogram slot ``ALIGN_MODEL_SLOT``: for every projection a, projection a of a SIRT reconstruction (``niter`` iterations
