@@ -298,6 +298,35 @@ int tomo_sino_median(tomo_engine *e, int src, int dst, int radius, const float *
                      double *out_host /* [Nproj][5] */);                                     /* waits */
 int tomo_sino_intensity(tomo_engine *e, int src, int dst, const float *gain_offset_host /* [Nproj][2] */, int clamp);   /* logger.py:261 */
 
+/* ---- marker (fiducial / feature) detection (kernels_markers.hip.h; the driver is TomoGPU.align_markers, the tracking and the
+ * least-squares model are tomo_tv_amd/align.py: link_markers, solve_markers) --------------------------------------------------
+ * An extension: the reference has no marker alignment.  Conventions of the conditioning block: projection a of a slot is the image
+ * X_a[r][s], 0 <= r < Nray, 0 <= s < Nslice; padding slices are never read as data and are zero in whatever is written; projections
+ * never mix.  One whole-volume engine only: TOMO_ERR_STATE on an engine with a communicator, a slab of a larger volume
+ * (tomo_set_slab_edges) or released geometry.  A refused call enqueues nothing and writes nothing.  Source slots are only read (no
+ * claim on TOMO_SINO_G is dropped unless G is the destination).  No floating-point atomics: the same bits from call to call.
+ *   tomo_sino_template_ncc: the zero-mean normalised cross-correlation of every projection with one (2R+1) x (2R+1) template,
+ *       template_host[k][j] at ray offset k - R and slice offset j - R, W = (2R+1)^2.  The library forms t = T - mean(T) scaled to
+ *       sum t^2 = 1 in binary64 and rounds it to binary32.  For a sample whose whole window lies inside the image, in binary32, every
+ *       operation rounded on its own and the window walked in row-major order from 0:  m = (sum x) / W;  c = sum t (x - m);
+ *       v = sum (x - m)^2;  dst = c / sqrt(v) where v > var_floor * W (one binary32 product), else 0.  A sample whose window leaves
+ *       the image gets 0 (so a projection smaller than the template is all zero).  Enqueued on the engine's stream, no wait (the
+ *       template is consumed before the call returns).  TOMO_ERR_ARG: R outside 1..8, src == dst, a constant or non-finite template,
+ *       a negative or NaN var_floor.
+ *   tomo_sino_peaks: the local maxima of every projection.  (r, s) is a peak iff x >= threshold and, for every other sample
+ *       (r', s') of its (2 radius + 1)^2 window clipped to the image, x > x' where (r', s') precedes (r, s) in row-major (r, s)
+ *       order and x >= x' where it follows: of a plateau exactly the first sample.  A NaN is never a peak, nor is a sample with a NaN
+ *       in its window.  count_host[a] = the true number of peaks of projection a, whatever capacity is.  records_host[a][k], for
+ *       k < min(count_host[a], capacity), = eight 32-bit words: r, s (int32), the binary32 values at (r, s), (r-1, s), (r+1, s),
+ *       (r, s-1), (r, s+1) -- a neighbour outside the image repeated as the centre value -- and a zero; sorted by r * Nslice + s
+ *       ascending.  Where count_host[a] > capacity the records of that projection are unspecified (call again with the capacity the
+ *       counts ask for); records past the count are not written.  Waits for its result.  TOMO_ERR_ARG: radius outside 1..8, a NaN
+ *       threshold, capacity < 1.
+ * TOMO_ERR_ARG also: a bad slot, a null pointer. */
+int tomo_sino_template_ncc(tomo_engine *e, int src, int dst, const float *template_host /* [2R+1][2R+1] */, int R, float var_floor);
+int tomo_sino_peaks(tomo_engine *e, int sino, int radius, float threshold, int capacity, int *count_host /* [Nproj] */,
+                    int *records_host /* [Nproj][capacity][8] */);                           /* waits */
+
 /* ---- binning and prolongation between two engines (coarse-to-fine drivers) --------------------------------------------------
  * `fine` and `coarse` are two different whole-volume engines on one device whose grids differ by factor = f, 2 or 4:
  *     fine Nray == f * coarse Nray,   coarse Nslice == ceil(fine Nslice / f),   and for tomo_sino_bin the same Nproj.

@@ -131,6 +131,8 @@ SIGNATURES = {
     "tomo_sino_window_stats": [_p, _i, _i, _i, _i, _i, _p],
     "tomo_sino_median": [_p, _i, _i, _i, _p, _p],
     "tomo_sino_intensity": [_p, _i, _i, _p, _i],
+    "tomo_sino_template_ncc": [_p, _i, _i, _p, _i, _f],
+    "tomo_sino_peaks": [_p, _i, _i, _f, _i, _p, _p],
     "tomo_sino_bin": [_p, _i, _p, _i, _i],
     "tomo_volume_bin": [_p, _i, _p, _i, _i],
     "tomo_volume_prolong": [_p, _i, _p, _i, _i],

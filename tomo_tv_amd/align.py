@@ -489,3 +489,203 @@ def mass_gains(moments):
     if not np.all(mass > 0) or not np.all(np.isfinite(mass)):
         raise ValueError("every projection needs a positive, finite total mass")
     return mass.mean() / mass
+
+
+# ---- marker (fiducial / feature) alignment: the host side of ``tomoengine.sino_template_ncc`` / ``sino_peaks`` ------------------------
+# Coordinates: an observation is (a, r, s) -- projection index, position along the rays, position along the tilt axis, in samples.  A
+# marker is (y, z, sigma): its position in a slice of the volume relative to the slice centre ((N-1)/2, (N-1)/2), in voxels along
+# the first and second axis of the (Nslice, N, N) volume, and its slice relative to the detector centre c_s = (Nslice-1)/2.
+MARKER_NCC_SLOT = SINO_USER0 + 36      # sinogram slot TomoGPU.align_markers writes the correlation into
+MARKER_MAX_MISSES = 2                  # a track ends after this many consecutive projections without a detection
+
+
+def marker_template(radius_px, R, bright=True):
+    """(2R+1, 2R+1) float64: an anti-aliased disc of radius ``radius_px`` about the window centre, the share of every sample's
+    unit square that the disc covers (8 x 8 sub-samples), 1 inside and 0 outside for a ``bright`` marker (a gold bead in a
+    dark-field or inverted series), the negative for a dark one.  ``ValueError`` when the result would be constant: a disc that
+    leaves no background inside the window, or none at all."""
+    R, rad = int(R), float(radius_px)
+    if R < 1 or not rad > 0.0 or not np.isfinite(rad):
+        raise ValueError("R must be at least 1 and radius_px positive and finite")
+    sub = (np.arange(8) + 0.5) / 8.0 - 0.5
+    g = (np.arange(-R, R + 1)[:, None] + sub[None, :]).ravel()
+    inside = (g[:, None] ** 2 + g[None, :] ** 2 <= rad * rad).astype(np.float64)
+    T = inside.reshape(2 * R + 1, 8, 2 * R + 1, 8).mean((1, 3))
+    if T.max() - T.min() <= 0.0:
+        raise ValueError("the disc fills the whole window (or none of it): the template would be constant")
+    return T if bright else -T
+
+
+def marker_positions(records, shape=None):
+    """(k, 2) float64 sub-pixel positions (r, s) from the (k, 8) int32 records of ``tomoengine.sino_peaks``: the integer position
+    plus, along each axis, the vertex of the parabola through the centre value and its two neighbours (``_parabola``: inside
+    +-0.5).  With ``shape`` = (N, Nslice) a peak on the image border keeps its integer position along that axis (its record
+    repeats the centre value there)."""
+    rec = np.ascontiguousarray(records, np.int32).reshape(-1, 8)
+    val = rec[:, 2:7].view(np.float32).astype(np.float64)
+    out = rec[:, :2].astype(np.float64)
+    for k in range(len(rec)):
+        r, s = int(rec[k, 0]), int(rec[k, 1])
+        if shape is None or 0 < r < int(shape[0]) - 1:
+            out[k, 0] += _parabola(val[k, 1], val[k, 0], val[k, 2])
+        if shape is None or 0 < s < int(shape[1]) - 1:
+            out[k, 1] += _parabola(val[k, 3], val[k, 0], val[k, 4])
+    return out
+
+
+def marker_detector_coordinate(angles_deg, N):
+    """(Nangles, 2) float64 rows ``u_a`` = (-sin theta_a, cos theta_a): a point at (y, z) voxels from the centre of a slice
+    (voxel index minus (N-1)/2 along the first and second axis of the slice) is seen in projection a at ray coordinate
+    ``(N-1)/2 + u_a . (y, z)``.  From the ray convention of sysmat.cpp: ray j passes through offset_j (cos, sin) with direction
+    (-sin, cos), offset_j = j - (N-1)/2, and voxel (iy, iz) is the unit square centred at x = iz - (N-1)/2, y_math = (N-1)/2 - iy
+    (column floor(N/2 - y_math) * N + floor(x + N/2)); a point lies on the ray whose offset is x cos + y_math sin."""
+    t = np.deg2rad(np.asarray(angles_deg, np.float64).ravel())
+    return np.stack([-np.sin(t), np.cos(t)], axis=1)
+
+
+def _nearest(P, Q):
+    """for every row of P the index of and the distance to the nearest row of Q (first on ties)"""
+    d = np.sqrt(((P[:, None, :] - Q[None, :, :]) ** 2).sum(2))
+    k = np.argmin(d, axis=1)
+    return k, d[np.arange(len(P)), k]
+
+
+def link_markers(positions, angles_deg, N, search_radius, min_views, max_misses=MARKER_MAX_MISSES, max_offset=None):
+    """Follow markers through the series.  ``positions[a]`` = (n_a, 2) detections (r, s) of projection a.  -> a list of tracks, each
+    a (k, 3) float64 array of rows (a, r, s) sorted by a, k >= ``min_views``.
+
+    The projection nearest zero tilt starts one track per detection; the others are visited outwards from it, first towards higher
+    indices, then towards lower ones.  In a visited projection every live track predicts its position: its last position, or, once
+    it has three points, the sinusoid ``(N-1)/2 + u_a . (y, z)`` fitted to them (``marker_detector_coordinate``) with the mean of its
+    s.  A shift of a whole projection moves all its detections together, so the predictions are first moved by one common offset:
+    among the differences (detection - prediction) no longer than ``max_offset`` (default 2 ``search_radius``: the shift of a
+    projection against the starting one), the one with the least sum over the tracks of
+    min(distance to the nearest detection, ``search_radius``)^2; no offset is a candidate too, and wins ties.
+    Tracks remember positions with that offset removed, so it does not enter later predictions.  Then a track takes the
+    detection nearest its moved prediction if that is within ``search_radius`` AND the track is that detection's nearest live
+    track: a choice that is not mutual is a miss.  A track ends after more than ``max_misses`` consecutive misses in one
+    direction (it can still grow in the other); a detection nobody took starts no new track."""
+    ang = np.asarray(angles_deg, np.float64).ravel()
+    P = len(ang)
+    if len(positions) != P:
+        raise ValueError("positions must hold one array per projection")
+    det = [np.asarray(p, np.float64).reshape(-1, 2) for p in positions]
+    rad = float(search_radius)
+    if not rad > 0.0 or int(min_views) < 1 or int(max_misses) < 0:
+        raise ValueError("search_radius must be positive, min_views at least 1 and max_misses not negative")
+    far = 2.0 * rad if max_offset is None else float(max_offset)
+    U, c = marker_detector_coordinate(ang, N), 0.5 * (N - 1)
+    a0 = int(np.argmin(np.abs(ang)))
+    # a track: {a: (observed r, observed s, r and s with the common offset removed)}
+    tracks = [{a0: (p[0], p[1], p[0], p[1])} for p in det[a0]]
+
+    def predict(tr, a):
+        pts = np.array([(k, v[2], v[3]) for k, v in sorted(tr.items())])
+        if len(pts) < 3:
+            last = pts[np.argmin(np.abs(pts[:, 0] - a))]
+            return last[1:]
+        yz = np.linalg.lstsq(U[pts[:, 0].astype(int)], pts[:, 1] - c, rcond=None)[0]
+        return np.array([c + U[a] @ yz, pts[:, 2].mean()])
+
+    for order in (range(a0 + 1, P), range(a0 - 1, -1, -1)):
+        misses = [0] * len(tracks)
+        for a in order:
+            live = [t for t in range(len(tracks)) if misses[t] <= int(max_misses)]
+            if not live or not len(det[a]):
+                for t in live:
+                    misses[t] += 1
+                continue
+            pred = np.array([predict(tracks[t], a) for t in live])
+            diff = (det[a][None, :, :] - pred[:, None, :]).reshape(-1, 2)
+            diff = diff[np.sqrt((diff ** 2).sum(1)) <= far]
+            diff = np.vstack([np.zeros((1, 2)), diff])                   # no offset is always a candidate, and the first
+            cost = [np.sum(np.minimum(_nearest(pred + o, det[a])[1], rad) ** 2) for o in diff]
+            off = diff[int(np.argmin(cost))]
+            moved = pred + off
+            kd, dd = _nearest(moved, det[a])
+            kt, _ = _nearest(det[a], moved)
+            for i, t in enumerate(live):
+                if dd[i] <= rad and kt[kd[i]] == i:
+                    q = det[a][kd[i]]
+                    tracks[t][a] = (q[0], q[1], q[0] - off[0], q[1] - off[1])
+                    misses[t] = 0
+                else:
+                    misses[t] += 1
+    out = [np.array([(a, v[0], v[1]) for a, v in sorted(tr.items())], np.float64) for tr in tracks]
+    return [t for t in out if len(t) >= int(min_views)]
+
+
+def marker_gauge(shifts, angles_deg):
+    """``(shifts', (alpha, beta, gamma))``: the shifts without the three modes that marker positions can absorb -- dr loses its
+    least-squares components alpha cos theta_a + beta sin theta_a, ds its mean gamma.  Moving every marker by (y, z, sigma) +=
+    (beta, -alpha, -gamma) explains the same observations."""
+    d = np.array(shifts, np.float64).reshape(-1, 2)
+    t = np.deg2rad(np.asarray(angles_deg, np.float64).ravel())
+    B = np.stack([np.cos(t), np.sin(t)], axis=1)
+    ab = np.linalg.lstsq(B, d[:, 0], rcond=None)[0]
+    g = float(d[:, 1].mean())
+    d[:, 0] -= B @ ab
+    d[:, 1] -= g
+    return d, (float(ab[0]), float(ab[1]), g)
+
+
+def solve_markers(tracks, angles_deg, N, Nslice, rotation=True):
+    """The least-squares marker model.  With R(phi) = [[cos, -sin], [sin, cos]] in (r, s), c = ((N-1)/2, (Nslice-1)/2) and
+    ``q = R(phi) (obs - c) + d_a`` -- where ``set_alignment(d, rotation_deg=phi)`` (``affine_matrices``) moves an observed position
+    to, relative to c -- the model is ``q = (u_a . (y_j, z_j), sigma_j)`` for marker j in projection a (``marker_detector_coordinate``).
+    Unknowns: (y, z, sigma) per marker, d_a per projection, and one in-plane rotation phi.
+
+    For a fixed phi the problem is linear and its matrix A does not depend on phi, while the right-hand side is
+    cos(phi) b0 + sin(phi) b1.  Variable projection therefore has a closed form: with g0, g1 the parts of b0, b1 outside the range
+    of A, phi minimises |cos(phi) g0 + sin(phi) g1| -- the right singular vector of [g0 g1] with the smallest singular value, taken
+    in (-90, 90] degrees.  ``rotation=False`` keeps phi = 0.  Then positions and shifts come from one linear solve.
+
+    Gauge: the returned shifts have no component along cos theta_a and sin theta_a in dr and no mean in ds (``marker_gauge``); the
+    marker positions carry those modes.  -> dict: ``shifts`` (Nangles, 2), ``rotation_deg``, ``markers`` (J, 3) of (y, z, sigma),
+    ``residuals`` (one (k, 2) array per track, q - model in pixels) and ``residual_rms`` (root mean square length over all
+    observations).  ``ValueError``: fewer than three markers, or observations that do not determine every unknown beyond the
+    gauge (a projection no track visits, a marker seen at too few angles)."""
+    ang = np.asarray(angles_deg, np.float64).ravel()
+    P, J = len(ang), len(tracks)
+    if J < 3:
+        raise ValueError(f"marker alignment needs at least three markers, got {J}")
+    U = marker_detector_coordinate(ang, N)
+    c = np.array([0.5 * (N - 1), 0.5 * (Nslice - 1)])
+    trk = [np.asarray(t, np.float64).reshape(-1, 3) for t in tracks]
+    nobs = sum(len(t) for t in trk)
+    A = np.zeros((2 * nobs, 3 * J + 2 * P))
+    b0, b1 = np.zeros(2 * nobs), np.zeros(2 * nobs)
+    row = 0
+    for j, t in enumerate(trk):
+        for a, r, s in t:
+            a = int(a)
+            if not 0 <= a < P:
+                raise ValueError(f"track {j} names projection {a} of {P}")
+            A[row, 3 * j:3 * j + 2] = U[a]
+            A[row + 1, 3 * j + 2] = 1.0
+            A[row, 3 * J + 2 * a] = A[row + 1, 3 * J + 2 * a + 1] = -1.0
+            o = np.array([r, s]) - c
+            b0[row:row + 2] = o
+            b1[row:row + 2] = (-o[1], o[0])
+            row += 2
+    Uu, sv, Vt = np.linalg.svd(A, full_matrices=False)
+    rank = int(np.sum(sv > 1e-10 * sv[0]))
+    if rank < A.shape[1] - 3:
+        raise ValueError(f"the tracks do not determine the model: rank {rank} where {A.shape[1] - 3} is needed beyond the gauge "
+                         "(every projection needs a tracked marker, every marker views at two or more tilts)")
+    Q = Uu[:, :rank]
+    phi = 0.0
+    if rotation:
+        G = np.stack([b0 - Q @ (Q.T @ b0), b1 - Q @ (Q.T @ b1)], axis=1)
+        v = np.linalg.svd(G, full_matrices=False)[2][-1]
+        if v[0] < 0.0 or (v[0] == 0.0 and v[1] < 0.0):
+            v = -v
+        phi = float(np.arctan2(v[1], v[0]))
+    b = np.cos(phi) * b0 + np.sin(phi) * b1
+    x = Vt[:rank].T @ ((Q.T @ b) / sv[:rank])
+    res = (b - A @ x).reshape(-1, 2)
+    shifts, (alpha, beta, gamma) = marker_gauge(x[3 * J:].reshape(P, 2), ang)
+    markers = x[:3 * J].reshape(J, 3) + np.array([beta, -alpha, -gamma])
+    cut = np.cumsum([len(t) for t in trk])[:-1]
+    return dict(shifts=shifts, rotation_deg=float(np.rad2deg(phi)), markers=markers, residuals=np.split(res, cut),
+                residual_rms=float(np.sqrt(np.mean((res ** 2).sum(1)))))

@@ -23,6 +23,7 @@
 #include "kernels_align_normal.hip.h" // per-projection similarity matching: gather, gradient and the 4 x 4 normal equations in one pass
 #include "kernels_tilt.hip.h"     // tilt-angle refinement: the rotational derivative of a volume, the per-projection sums of the angle step
 #include "kernels_condition.hip.h" // conditioning of a tilt series: window statistics, local median, gain and offset
+#include "kernels_markers.hip.h"  // marker detection: template NCC of every projection, local maxima with their neighbours
 #include "kernels_bin.hip.h"      // binning of sinograms and volumes by 2 or 4, trilinear prolongation
 #include "kernels_dual.hip.h"     // dual-axis: the volume transposed between two engines with perpendicular tilt axes
 #include "kernels_affine3d.hip.h" // a volume resampled by a 3-D affine map (trilinear, binary64 coordinates)

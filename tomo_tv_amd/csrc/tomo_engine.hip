@@ -290,6 +290,12 @@ struct tomo_engine {
     float *al_mean = nullptr;
     size_t al_part_bytes = 0, al_out_bytes = 0;
     std::vector<float> cond_tab;                  // conditioning (engine_condition.inc): the host copy of the last {gain, offset} table enqueued
+    // marker detection (engine_markers.inc): the host copy of the last normalised template enqueued; the peak counters and records on
+    // the device (kept, grown on demand) and the host block the records are sorted in
+    std::vector<float> mk_tmpl;
+    void *mk_buf = nullptr;
+    size_t mk_bytes = 0;
+    std::vector<int> mk_host;
     // DART (engine_dart.inc): one state byte per voxel, the number of thresholds it was made with (-1: no segmentation yet), and the
     // class statistics' partial sums [DART_STATS_BLOCKS + 1][16][2] (the last row: the result)
     uint8_t *dart_state = nullptr;
@@ -511,6 +517,7 @@ extern "C" {
 #include "engine_align.inc"
 #include "engine_tilt.inc"
 #include "engine_condition.inc"
+#include "engine_markers.inc"
 #include "engine_bin.inc"
 #include "engine_dual.inc"
 #include "engine_affine3d.inc"

@@ -429,6 +429,7 @@ class _GroupBackend:
     c_volume_affine = c_volume_affine_axpy = c_volume_affine_normal = _no_align
     c_volume_rot_derivative = c_sino_tilt_normal = _no_align
     c_sino_window_stats = c_sino_median = c_sino_intensity = _no_align
+    c_sino_template_ncc = c_sino_peaks = _no_align
 
     def c_set_tilt_series(self, ptr):
         self._rows("set_sinogram", SINO_B, ptr, self.nray * self.nproj * 4)
@@ -1144,6 +1145,36 @@ class _EngineBase:
         tab[:, 0] = np.broadcast_to(np.asarray(gain, np.float32), (self.Nproj,))
         tab[:, 1] = np.broadcast_to(np.asarray(offset, np.float32), (self.Nproj,))
         self.be.c("sino_intensity", int(src), int(dst), _ptr(tab), int(bool(clamp)))
+
+    # ---- marker detection (include/tomo_hip.h: tomo_sino_template_ncc / tomo_sino_peaks; tracking and the least-squares model are
+    # in align.py, the driver is TomoGPU.align_markers) ---------------------------------------------------------------------------
+    def sino_template_ncc(self, src, dst, template, var_floor=0.0):
+        """Slot ``dst`` != ``src`` receives the zero-mean normalised cross-correlation of every projection of slot ``src`` with the
+        square ``template`` ((2R+1, 2R+1), R in 1..8; index [ray offset + R][slice offset + R]; the library removes its mean and
+        scales it to unit norm): values in [-1, 1], 0 where the window leaves the image or its variance sum is not above
+        ``var_floor * (2R+1)^2``.  Enqueued, no wait."""
+        self._align_one_engine()
+        T = np.ascontiguousarray(template, np.float32)
+        if T.ndim != 2 or T.shape[0] != T.shape[1] or T.shape[0] % 2 != 1:
+            raise ValueError("the template must be a square array of odd size")
+        self.be.c("sino_template_ncc", int(src), int(dst), _ptr(T), (T.shape[0] - 1) // 2, float(var_floor))
+
+    def sino_peaks(self, sino, radius, threshold, capacity=256):
+        """The local maxima of every projection of slot ``sino``: samples >= ``threshold`` that are the first maximum (row-major) of
+        their (2 ``radius`` + 1)^2 window clipped to the image.  -> ``(count (Nproj,) int32, records)``, ``records[a]`` a
+        (count[a], 8) int32 array sorted by r * Nslice + s: columns r, s, then the bits of the binary32 values at (r, s), (r-1, s),
+        (r+1, s), (r, s-1), (r, s+1) (``.view(np.float32)``; a neighbour outside the image repeated as the centre) and a zero.
+        ``capacity`` sizes the first call; where a projection holds more peaks the call is repeated once with the largest count, so
+        the result is always complete."""
+        self._align_one_engine()
+        count = np.zeros(self.Nproj, np.int32)
+        cap = max(1, int(capacity))
+        while True:
+            rec = np.zeros((self.Nproj, cap, 8), np.int32)
+            self.be.c("sino_peaks", int(sino), int(radius), float(threshold), cap, _ptr(count), _ptr(rec))
+            if int(count.max(initial=0)) <= cap:
+                return count.copy(), [rec[a, :count[a]].copy() for a in range(self.Nproj)]
+            cap = int(count.max())
 
     def sino_affine(self, src, dst, matrices):
         """dst_p[r][s] = src_p(r', s'), bilinear, zeros outside the image, with r' = m00 r + m01 s + m02, s' = m10 r + m11 s + m12 and

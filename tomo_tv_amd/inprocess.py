@@ -251,6 +251,7 @@ class InProcessMultiGPU:
 
     sino_moments = sino_xcorr = sino_shift = sino_affine = sino_axis_profile = sino_affine_normal = _align_one_engine = _no_align
     sino_window_stats = sino_median = sino_intensity = _no_align
+    sino_template_ncc = sino_peaks = _no_align
     bin_sinogram_to = bin_volume_to = prolong_volume_to = _no_align      # (two whole-volume engines: engine.py)
     cross_volume_to = cross_axpy_volume_to = volume_affine_to = volume_affine_axpy_to = volume_affine_normal = _no_align
 

@@ -566,6 +566,40 @@ class TomoGPU:
             out["gain"] = self.normalize_intensity(**pick("mode"))
         return out
 
+    # ---- marker (fiducial / feature) alignment: detection on the device (include/tomo_hip.h: tomo_sino_template_ncc /
+    # tomo_sino_peaks), tracking and the least-squares model in align.py.  An extension: the reference has none. -----------------
+    MARKER_NCC_SLOT = align.MARKER_NCC_SLOT   # SINO_USER0 + 36: the correlation of the series as given with the marker template
+
+    def align_markers(self, marker_radius=2.0, R=None, bright=True, threshold=0.5, peak_radius=None, search_radius=6.0, min_views=None,
+                      rotation=True, apply=True):
+        """First alignment from tracked markers, without a reconstruction: the series as given is correlated with an anti-aliased disc
+        of radius ``marker_radius`` samples (``align.marker_template``; window radius ``R``, default ceil(marker_radius) + 2, at most
+        8; ``bright=False`` for dark markers) into sinogram slot ``MARKER_NCC_SLOT``; its local maxima >= ``threshold`` within
+        ``peak_radius`` (default ``R``) are the detections, refined to sub-pixel positions (``align.marker_positions``), followed
+        through the series (``align.link_markers`` with ``search_radius``; tracks with fewer than ``min_views`` views, default half
+        the projections, are dropped) and fitted by ``align.solve_markers``: marker positions, one shift per projection and, with
+        ``rotation``, the in-plane rotation of the tilt axis.  With ``apply`` the result goes to
+        ``set_alignment(shifts, rotation_deg=phi)``, which resamples the series as given once.  -> dict: ``shifts`` (Nangles, 2),
+        ``rotation_deg``, ``markers`` (J, 3) of (y, z, sigma), ``tracks``, ``residual_rms`` (pixels: how good the alignment is),
+        ``n_detected`` (Nangles,); also kept as ``self.marker_alignment``."""
+        t = self._align_engine()
+        R = int(np.ceil(float(marker_radius))) + 2 if R is None else int(R)
+        peak_radius = R if peak_radius is None else int(peak_radius)
+        min_views = max(3, (self.Nangles + 1) // 2) if min_views is None else int(min_views)
+        t.sino_template_ncc(self.ALIGN_SLOT, self.MARKER_NCC_SLOT, align.marker_template(marker_radius, R, bright))
+        count, records = t.sino_peaks(self.MARKER_NCC_SLOT, peak_radius, threshold)
+        positions = [align.marker_positions(rec, (self.Nray, self.Nslice)) for rec in records]
+        tracks = align.link_markers(positions, self._tilt_deg, self.Nray, search_radius, min_views)
+        out = align.solve_markers(tracks, self._tilt_deg, self.Nray, self.Nslice, rotation=rotation)
+        out = dict(shifts=out["shifts"], rotation_deg=out["rotation_deg"], markers=out["markers"], tracks=tracks,
+                   residual_rms=out["residual_rms"], n_detected=count.astype(np.int64))
+        self.marker_alignment = out
+        if apply:
+            self.set_alignment(out["shifts"], rotation_deg=out["rotation_deg"])
+            self._pyramid = {}                     # binned copies and a reconstruction of the series as it was aligned before
+            self.recon = None
+        return out
+
     def _model_leave_one_out(self, niter):
         """Into sinogram slot ``ALIGN_MODEL_SLOT``: for every projection a, projection a of a SIRT reconstruction (``niter`` iterations
         from zero) that never saw projection a.  One engine does it: before every SIRT step the data of projection a are replaced by
