@@ -498,6 +498,43 @@ int tomo_dart_arm(tomo_engine *e, int vol, int sino_b, int niter, const float *g
 int tomo_dart_smooth(tomo_engine *e, int src, int dst, float beta);
 int tomo_dart_class_stats(tomo_engine *e, int vol, const float *thr_host, int nthr, double *out_host); /* [nthr+1][2], waits */
 int tomo_dart_get_state(tomo_engine *e, uint8_t *out_host);  /* [Nslice][Ny][Nz], waits */
+
+/* ---- Connected components of a thresholded volume: labels, per-component measurements, removal of components ----------------------
+ * The reference has no counterpart (its users label the downloaded volume on the host); these calls close the workflow on the
+ * resident volume, and TomoGPU.label_particles (reconstructor.py) is the driver.  A voxel v = (s, y, z) as for the DART calls;
+ * its public linear index is p = (s N + y) N + z.
+ *   foreground: fg(v) = lo <= x(v) && x(v) <= hi, compared in binary32: a NaN voxel is never foreground; lo = -Inf and hi = +Inf are
+ *       allowed.  The pitch padding of a volume is never foreground and never read.
+ *   connectivity: 6 = the faces, 26 = faces, edges and corners.  Neighbours are NOT periodic.
+ *   numbering: the components are numbered 1..K in ascending order of their smallest p; background is 0 (the numbering of
+ *       scipy.ndimage.label).  The rule fixes every label whatever the order in which the kernels' atomics arrive.
+ *   tomo_components_label: labels slot `vol` (read only) into the engine's label state -- one int32 per voxel, a root count per
+ *       256 voxels and K records, allocated here and kept -- and returns K in *count.  Waits.
+ *   tomo_components_get_labels: the labels as [Nslice][Ny][Nz] int32.  Waits.
+ *   tomo_components_stats: records 1..min(K, capacity) in component order; nothing beyond them is written.  All fields are integers,
+ *       hence exact in any order of accumulation: voxels; sum_s, sum_y, sum_z (the centroid is sum / voxels, formed by the host);
+ *       the bounding box min_* .. max_* (inclusive); first = the component's smallest p; surface = the number of its voxels with at
+ *       least one of the SIX face neighbours background or outside the volume, whatever connectivity labelled it.  The measurements
+ *       are taken by the first call after a labelling and kept with it.  Sums of intensities are not offered: a floating-point sum
+ *       over an arbitrary voxel set has no fixed order without a sort.  Waits.
+ *   tomo_components_keep: x(v) = fill where label(v) > 0 && !keep_host[label(v)]; every other voxel keeps its bits (it is not
+ *       written).  n must be K + 1 (entry 0, the background's, is not read).  The label state is NOT changed: label again for
+ *       contiguous numbers.  Enqueued, no wait; the table goes through the staging buffer in stream order.
+ *   tomo_components_release: frees the label state (4 bytes per voxel); allowed on any engine, a no-op without a state.
+ * The same labels, K and records from run to run and on a used engine as on a fresh one.
+ * TOMO_ERR_STATE: get_labels, stats or keep without a labelling; an engine bound to a communicator, or one whose geometry was
+ * released (one whole-volume engine only, as for the DART calls: the Python classes refuse slabs of a larger volume before the call).
+ * TOMO_ERR_ARG: a null engine or pointer, a bad slot, connectivity other than 6 or 26, a NaN bound or lo > hi, n != K + 1, a negative
+ * capacity, or Nslice * N * N >= 2^31 (label + 1 must fit int32).  A refused call has enqueued and allocated nothing. */
+typedef struct tomo_component {
+    int64_t voxels, sum_s, sum_y, sum_z, surface, first;
+    int32_t min_s, min_y, min_z, max_s, max_y, max_z;
+} tomo_component;                                            /* 72 bytes; _lib.COMPONENT_DTYPE mirrors it */
+int tomo_components_label(tomo_engine *e, int vol, float lo, float hi, int connectivity, int64_t *count);   /* waits */
+int tomo_components_get_labels(tomo_engine *e, int32_t *labels_host);   /* [Nslice][Ny][Nz], waits */
+int tomo_components_stats(tomo_engine *e, int64_t capacity, tomo_component *records_host);   /* waits */
+int tomo_components_keep(tomo_engine *e, int vol, const uint8_t *keep_host, int64_t n, float fill);
+int tomo_components_release(tomo_engine *e);
 int tomo_read_scalars(tomo_engine *e, double *out, int count);          /* synchronises the stream */
 /* the same without a pipeline bubble: _snapshot enqueues the copy of all slots behind the kernels that produce them (and behind
  * an evaluation in flight on the second stream) and returns; _read waits for that copy only.  The ASD-POCS drivers enqueue the

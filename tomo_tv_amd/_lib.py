@@ -26,6 +26,10 @@ FORM_FP = ("rows", "tile", "strip", "list")
 FORM_BP = ("all", "tile", "list")
 FORM_SART = ("angle", "tile", "resident")
 
+# struct tomo_component (include/tomo_hip.h) as the fields of a numpy structured dtype: 72 bytes, no padding
+COMPONENT_FIELDS = [(k, "<i8") for k in ("voxels", "sum_s", "sum_y", "sum_z", "surface", "first")] + \
+                   [(k, "<i4") for k in ("min_s", "min_y", "min_z", "max_s", "max_y", "max_z")]
+
 _i, _i64, _f, _p = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 _u32 = ctypes.c_uint32
 _pp = ctypes.POINTER(ctypes.c_void_p)
@@ -148,6 +152,11 @@ SIGNATURES = {
     "tomo_dart_smooth": [_p, _i, _i, _f],
     "tomo_dart_class_stats": [_p, _i, _p, _i, _p],
     "tomo_dart_get_state": [_p, _p],
+    "tomo_components_label": [_p, _i, _f, _f, _i, ctypes.POINTER(_i64)],
+    "tomo_components_get_labels": [_p, _p],
+    "tomo_components_stats": [_p, _i64, _p],
+    "tomo_components_keep": [_p, _i, _p, _i64, _f],
+    "tomo_components_release": [_p],
     "tomo_fgp_begin_vol": [_p, _i],
     "tomo_tv_fgp_vol": [_p, _i, _i, _f],
     "tomo_bind_fgp_halo": [_p, _p, _p, _p, _p],

@@ -29,3 +29,4 @@
 #include "kernels_affine3d.hip.h" // a volume resampled by a 3-D affine map (trilinear, binary64 coordinates)
 #include "kernels_register3d.hip.h" // rigid registration of two volumes: gather, gradient and the 6 x 6 normal equations in one pass
 #include "kernels_dart.hip.h"    // DART: label / boundary / free-set stencil, masked restore and smoother, per-class sums
+#include "kernels_components.hip.h" // connected components: union-find labelling, renumbering scan, integer measurements, removal

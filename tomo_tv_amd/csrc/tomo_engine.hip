@@ -301,6 +301,15 @@ struct tomo_engine {
     uint8_t *dart_state = nullptr;
     int dart_nthr = -1;
     double *dart_part = nullptr;
+    // connected components (engine_components.inc): one int32 label per real voxel in the public order, the root counts of every 256
+    // voxels (then their prefix sums and K), the K records and the room they have, K itself (-1: no labelling), whether the records
+    // hold the measurements of this labelling yet, and the host copy of the last keep table enqueued
+    int *cc_label = nullptr, *cc_counts = nullptr;
+    CcRecord *cc_rec = nullptr;
+    size_t cc_rec_cap = 0;
+    int64_t cc_count = -1;
+    bool cc_stats_done = false;
+    std::vector<uint8_t> cc_keep;
     // registration (engine_register3d.inc): the workgroups' partial sums of the normal equations [RG_BLOCKS + 1][32] (the last row: the result)
     double *reg_part = nullptr;
     // scalars
@@ -523,6 +532,7 @@ extern "C" {
 #include "engine_affine3d.inc"
 #include "engine_register3d.inc"
 #include "engine_dart.inc"
+#include "engine_components.inc"
 #include "engine_comm.inc"
 #include "engine_options.inc"
 

@@ -1395,6 +1395,51 @@ class _EngineBase:
         self.be.c("dart_get_state", _ptr(out))
         return out
 
+    # ---- connected components (include/tomo_hip.h: tomo_components_*; the driver is TomoGPU.label_particles) -----------------------
+    def _components_one_engine(self):
+        """One whole-volume engine: a component crosses slab boundaries."""
+        if self.comm is not None or self.sub_slabs > 1 or not isinstance(self.be, _SlabBackend):
+            raise NotImplementedError("component labelling runs on one whole-volume engine (not on slabs sharded over ranks, devices "
+                                      "or sub_slabs)")
+
+    def label_components(self, vol, lo, hi, connectivity=26):
+        """Label the 6- or 26-connected components of ``lo <= x <= hi`` (binary32; a NaN is background) in volume ``vol``: numbers
+        1..K in ascending order of a component's smallest index (s Ny + y) Nz + z, the numbering of ``scipy.ndimage.label``.  -> K."""
+        self._components_one_engine()
+        k = ctypes.c_int64(-1)
+        self.be.c("components_label", int(vol), float(lo), float(hi), int(connectivity), ctypes.byref(k))
+        self._n_components = int(k.value)
+        return self._n_components
+
+    def component_labels(self):
+        """(Nslice, Nray, Nray) int32: 0 for background, 1..K for the components of the last ``label_components``."""
+        self._components_one_engine()
+        out = np.empty((self.Nslice_, self.Ny, self.Ny), np.int32)
+        self.be.c("components_get_labels", _ptr(out))
+        return out
+
+    def component_stats(self):
+        """A structured array (``_lib.COMPONENT_FIELDS``) of K records, record k - 1 for component k: ``voxels``, ``sum_s / _y / _z``,
+        the inclusive bounding box ``min_* / max_*``, ``first`` (its smallest index) and ``surface`` (voxels with a face neighbour
+        that is background or outside the volume).  All integers, hence exact."""
+        self._components_one_engine()
+        k = getattr(self, "_n_components", None)
+        out = np.zeros(max(k or 0, 0), np.dtype(_lib.COMPONENT_FIELDS))
+        self.be.c("components_stats", int(out.size), _ptr(out))     # (refuses, like the other queries, where there is no labelling)
+        return out
+
+    def keep_components(self, vol, keep, fill=0.0):
+        """``x = fill`` on every voxel of volume ``vol`` whose component k has ``keep[k]`` false; ``keep`` has K + 1 entries (entry 0
+        is the background's and is not read).  Every other voxel keeps its bits; the labels stay as they are."""
+        self._components_one_engine()
+        tab = np.ascontiguousarray(np.asarray(keep).astype(bool).ravel(), dtype=np.uint8)
+        self.be.c("components_keep", int(vol), _ptr(tab), int(tab.size), float(fill))
+
+    def release_components(self):
+        """Give the label state back (4 bytes per voxel)."""
+        self.be.c("components_release")
+        self._n_components = None
+
     def synchronize(self):
         self.be.c("synchronize")
 

@@ -252,6 +252,12 @@ class InProcessMultiGPU:
     sino_moments = sino_xcorr = sino_shift = sino_affine = sino_axis_profile = sino_affine_normal = _align_one_engine = _no_align
     sino_window_stats = sino_median = sino_intensity = _no_align
     sino_template_ncc = sino_peaks = _no_align
+
+    # a component crosses the devices' slabs (engine.py: _components_one_engine)
+    def _no_components(self, *args, **kw):
+        raise NotImplementedError("component labelling runs on one whole-volume engine, not on slabs spread over devices")
+
+    label_components = component_labels = component_stats = keep_components = release_components = _components_one_engine = _no_components
     bin_sinogram_to = bin_volume_to = prolong_volume_to = _no_align      # (two whole-volume engines: engine.py)
     cross_volume_to = cross_axpy_volume_to = volume_affine_to = volume_affine_axpy_to = volume_affine_normal = _no_align
 

@@ -33,6 +33,23 @@ def dart_thresholds(levels):
     return (0.5 * (g[:-1] + g[1:])).astype(np.float32)
 
 
+def particles_to_keep(voxels, min_voxels):
+    """The table ``keep_components`` takes, (K + 1,) bool: entry k is true where component k has at least ``min_voxels`` voxels
+    (entry 0, the background's, is true)."""
+    return np.concatenate([[True], np.asarray(voxels, dtype=np.int64) >= int(min_voxels)])
+
+
+def particle_table(stats):
+    """The records of ``component_stats`` as the dict ``TomoGPU.label_particles`` returns (centroids and diameters in binary64)."""
+    v = stats["voxels"].astype(np.float64)
+    return {"count": int(stats.size), "voxels": stats["voxels"].astype(np.int64),
+            "centroid": np.stack([stats["sum_s"] / v, stats["sum_y"] / v, stats["sum_z"] / v], axis=1).reshape(-1, 3),
+            "bbox": np.stack([np.stack([stats["min_s"], stats["min_y"], stats["min_z"]], axis=1),
+                              np.stack([stats["max_s"], stats["max_y"], stats["max_z"]], axis=1)], axis=1).reshape(-1, 2, 3).astype(np.int64),
+            "surface": stats["surface"].astype(np.int64), "equivalent_diameter": np.cbrt(6.0 * v / np.pi),
+            "first": stats["first"].astype(np.int64)}
+
+
 def device_count():
     """List of visible GPU ids (tomofusion/__init__.py:10-18)."""
     return list(range(_lib.device_count()))
@@ -934,6 +951,51 @@ class TomoGPU:
     def get_dart_labels(self):
         """(Nslice, Nray, Nray) uint8: the label (index into the grey levels) of every voxel in the last segmentation."""
         return self._dart_engine().dart_state() & _lib.DART_LABEL_MASK
+
+    # ---- particles: connected components of the thresholded reconstruction (an extension; engine.py *_components) -----------------
+    def _components_engine(self):
+        t = self.tomo
+        if not hasattr(t, "_components_one_engine"):
+            raise NotImplementedError("component labelling runs on one whole-volume engine, not on a volume sharded over devices")
+        t._components_one_engine()
+        return t
+
+    def label_particles(self, threshold=None, level=None, connectivity=26, min_voxels=1, fill=0.0):
+        """The particle table of the current reconstruction: its connected components (6 or 26 neighbours) on the device.
+
+        Foreground is ``x >= threshold``; ``threshold=None`` takes the midpoint of the two levels of ``estimate_grey_levels(2)``.
+        ``level=(g, tol)`` selects ``g - tol <= x <= g + tol`` instead: one grey level of a DART result.  ``min_voxels > 1`` sets
+        the components with fewer voxels to ``fill`` IN THE RECONSTRUCTION (``keep_components``) and labels again, so that the
+        numbers stay contiguous.  -> dict: ``count`` K and, per particle in label order (ascending smallest voxel index, the
+        numbering of ``scipy.ndimage.label``), ``voxels``, ``centroid`` (K, 3) float64 in (s, y, z), ``bbox`` (K, 2, 3) inclusive
+        min / max, ``surface`` (voxels with a face neighbour outside the particle), ``equivalent_diameter`` (of the sphere with
+        ``voxels``) and ``first``.  ``get_particle_labels()`` gives the label volume."""
+        t = self._components_engine()
+        if level is not None:
+            if threshold is not None:
+                raise ValueError("give a threshold or a level, not both")
+            g, tol = (float(v) for v in level)
+            if not tol >= 0.0:
+                raise ValueError("the tolerance of a level must not be negative")
+            lo, hi = g - tol, g + tol
+        else:
+            if threshold is None:
+                threshold = float(np.mean(self.estimate_grey_levels(2)))
+            lo, hi = float(threshold), float("inf")
+        if int(min_voxels) < 1:
+            raise ValueError("min_voxels must be at least 1")
+        t.label_components(VOL_RECON, lo, hi, connectivity)
+        st = t.component_stats()
+        keep = particles_to_keep(st["voxels"], min_voxels)
+        if not keep[1:].all():
+            t.keep_components(VOL_RECON, keep, fill)
+            t.label_components(VOL_RECON, lo, hi, connectivity)
+            st = t.component_stats()
+        return particle_table(st)
+
+    def get_particle_labels(self):
+        """(Nslice, Nray, Nray) int32: 0 for background, k for the voxels of particle k of the last ``label_particles``."""
+        return self._components_engine().component_labels()
 
     def _tensor_engine(self):
         if not hasattr(self.tomo, "get_volume_tensor") or getattr(self.tomo, "comm", None) is not None:
